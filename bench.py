@@ -1,7 +1,16 @@
 """Benchmark: env-steps/s of the fused HIP Z-Bot env.step on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--envs E] [--config c1|c2|c3|c5]
+                    [--full] [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run does what the headline needs and nothing else: it sets up, runs the W warm-up steps,
+times the K steps and prints the line. --full adds every other leg (the C2 rollout as stated, the
+PPO inputs, the actor in the loop, the rollout pipeline, the other models, solvers and physics
+switches, the CPU twin's baseline), each in the line under its own key; the --no-* options drop
+single legs of a --full run. --dump-outputs DIR writes what the last timed step returned to its
+caller as DIR/<name>.npy (dump_outputs); the inputs depend only on the arguments, so two builds
+run with the same arguments can be compared output for output.
 
 --gpus N is authoritative: without torchrun (WORLD_SIZE unset) and N > 1, bench.py spawns the N
 rank processes itself; under torchrun WORLD_SIZE must equal N; with nccl (RCCL) N GPUs must be
@@ -646,6 +655,33 @@ def bench_rollout_pipeline(eng, n: int, T: int, reps: int, dev, world: int, inlo
     }
 
 
+# the outputs of a step(extras=False) call that the step writes (obs_extra is not written then)
+DUMP_NAMES = ("obs_actor", "obs_critic", "reward_terms", "reward", "done", "success")
+DUMP_BUDGET = 64 * 10**6  # bytes of all dumped arrays together
+
+
+def dump_outputs(outputs: dict, path: str) -> dict:
+    """--dump-outputs: the arrays the last timed step returned to its caller (EnvGroups / HipEngine
+    .step(extras=False): the DUMP_NAMES entries, [n, ...] each), written as path/<name>.npy in
+    float32. If they hold more than DUMP_BUDGET bytes together, the same seeded sample of env rows of
+    every array is written instead, with the rows' env indices in path/env_index.npy (float64).
+    Returns {name: shape} of what was written."""
+    import numpy as np  # noqa: PLC0415
+
+    arrs = {k: outputs[k].detach().cpu().numpy().astype(np.float32) for k in DUMP_NAMES}
+    n = arrs["reward"].shape[0]
+    per_env = sum(a.nbytes for a in arrs.values()) // n + 8  # + the row's env index
+    keep = (DUMP_BUDGET - 4096) // per_env  # 4096: the .npy headers
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: a[idx] for k, a in arrs.items()}
+        arrs["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
+
+
 def _free_port() -> int:
     import socket  # noqa: PLC0415
 
@@ -751,6 +787,12 @@ def main(argv: list | None = None) -> None:
     ap.add_argument("--policy-groups", type=int, default=3,
                     help="env groups of the actor-in-the-loop legs (two-wave slot-sized actor layout; DESIGN.md §4f); "
                          "1 = one handle, 8-wave actor, current stream")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg of the line (c2_rollout, ppo_inputs, policy_in_loop, "
+                         "rollout_pipeline, the extra legs, cpu_baseline); the --no-* options drop single ones. "
+                         "Without it only the headline runs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the outputs of the last one (rank 0's envs) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-sec", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ppo", action="store_true", help="skip the post-rollout PPO-inputs leg")
@@ -840,27 +882,31 @@ def main(argv: list | None = None) -> None:
         # all_gather and a sequential rank-order sum (zbot_amd.dist.reduce_fixed_order: bit-reproducible)
         return reduce_episode_stats(eng.get_stats(clear=False))
 
-    # The other legs run first: their work (about two seconds of GPU time) brings the GPU to its
+    # The other legs (--full) run first: their work (about two seconds of GPU time) brings the GPU to its
     # steady clocks before the headline's own W warm-up steps and K timed steps; in a fresh
-    # process the first timed window otherwise ran ~4 % slower kernels (profiles/r03_v3_probe20_g*.json)
-    c2_leg = None if args.no_c2_rollout else bench_c2_rollout(eng, n, 256, dev, rank, world)
-    ppo_leg = None if args.no_ppo else bench_ppo_inputs(n, 256, 20, dev, world)
+    # process the first timed window otherwise ran ~4 % slower kernels (profiles/r03_v3_probe20_g*.json).
+    # A plain run has only its W warm-up steps for that: a short window (K = 20 after W = 5) reads
+    # about 4 % below the same window of a --full run, 200 steps and more read the same
+    full = args.full
+    c2_leg = None if not full or args.no_c2_rollout else bench_c2_rollout(eng, n, 256, dev, rank, world)
+    ppo_leg = None if not full or args.no_ppo else bench_ppo_inputs(n, 256, 20, dev, world)
     # the actor-in-the-loop legs: one handle on the current stream for the actor's kernel time, and
     # args.policy_groups env groups with the slot-sized two-wave actor
     eng1 = eng if G == 1 else None
     engp = None
-    if not (args.no_policy and args.no_pipeline):
+    run_policy, run_pipe = full and not args.no_policy, full and not args.no_pipeline
+    if run_policy or run_pipe:
         if G > 1:
             eng1 = HipEngine(cm, cfg, n, env_offset=rank * n, device=dev.index, seed=args.seed)
         if args.policy_groups > 1:
             engp = EnvGroups(cm, cfg, n, groups=args.policy_groups, env_offset=rank * n, device=dev.index,
                              seed=args.seed)
-    policy_leg = None if args.no_policy else bench_policy_in_loop(eng1, n, 48, dev, rank, engp)
-    pipe_leg = None if args.no_pipeline else bench_rollout_pipeline(engp or eng1, n, 32, 2, dev, world,
+    policy_leg = None if not run_policy else bench_policy_in_loop(eng1, n, 48, dev, rank, engp)
+    pipe_leg = None if not run_pipe else bench_rollout_pipeline(engp or eng1, n, 32, 2, dev, world,
                                                                      args.inloop_critic)
 
     extra_legs = {}
-    if not args.no_extra_legs and args.config == "c2" and args.model is None:
+    if full and not args.no_extra_legs and args.config == "c2" and args.model is None:
         extra_legs["ksim_env"] = bench_ksim_env(cm, n, args.steps, args.warmup, dev, rank, world, args.seed)
         extra_legs["train_defaults"] = bench_train_defaults(cm, dev, rank, world, args.seed)
         extra_legs["c1_gpu"] = bench_c1(cm, dev, rank, world, args.seed)
@@ -927,10 +973,10 @@ def main(argv: list | None = None) -> None:
     for t in range(args.steps):
         a_t = acts[(args.warmup + t) % acts.shape[0]]
         if G > 1:
-            eng.step(a_t, extras=False, events=ev[t])
+            last = eng.step(a_t, extras=False, events=ev[t])
         else:
             ev[t][0][0].record(stream)
-            eng.step(a_t, extras=False)
+            last = eng.step(a_t, extras=False)
             ev[t][0][1].record(stream)
     if G > 1:
         eng.join()
@@ -946,6 +992,7 @@ def main(argv: list | None = None) -> None:
     elapsed = float(el_t.item())
 
     eng.check()  # no launch flagged its results invalid (zb_check)
+    dumped = dump_outputs(last, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     kern_ms = [a.elapsed_time(b) for evt in ev for a, b in evt]
     avg_ms = sum(kern_ms) / len(kern_ms)
     wall_ms = 1e3 * elapsed / args.steps
@@ -987,6 +1034,7 @@ def main(argv: list | None = None) -> None:
             "ranks_seen": dist.get_world_size() if dist.is_initialized() else 1,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": "weak",
@@ -1064,7 +1112,9 @@ def main(argv: list | None = None) -> None:
         for k, leg in extra_legs.items():
             leg["vs_headline"] = leg["env_steps_per_s"] / value
             out[k] = leg
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if world == 1 and full and not args.no_cpu_baseline:
             if args.config == "c1":  # the whole C1 rollout on the CPU twin: 64 envs x 128 env-steps
                 out["cpu_baseline"] = cpu_baseline(cm, cfg, args.cpu_baseline_sec, "C1", n_envs=n, max_steps=128,
                                                    c1_leg=False)

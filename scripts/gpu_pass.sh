@@ -4,8 +4,8 @@
 # check: the -m gpu suite (prints the measured parity errors) and smoke
 # pmc:   PMC traffic / VALU passes of the step kernel and the GAE kernel (refreshes profiles/pmc_*)
 # trace: rocprofv3 kernel trace + stats of the headline's command
-# bench: the default bench line (the driver's N = 1 command)
-# c3c5:  bench lines at C3 and C5
+# bench: the whole bench line (bench.py --full: the headline and every other leg)
+# c3c5:  bench lines at C3 and C5 (--full without the CPU baseline and the extra legs)
 # Every step has its own time limit; the first failure ends the pass. Outputs: gpurun_out/<tag>/.
 set -e -o pipefail
 cd "$(dirname "$0")/.."
@@ -33,11 +33,11 @@ for step in "$@"; do
         --steps 32 --warmup 4 --no-cpu-baseline --no-ppo --no-policy --no-pipeline --no-c2-rollout --no-extra-legs > $O/trace_bench.log 2>&1
       cp gpurun_out/trace/run_kernel_stats.csv $O/kernel_stats.csv ;;
     bench)
-      timeout -k 10 600 python3 bench.py > $O/bench.json 2> $O/bench.err
+      timeout -k 10 600 python3 bench.py --full > $O/bench.json 2> $O/bench.err
       cat $O/bench.json ;;
     c3c5)
-      timeout -k 10 300 python3 bench.py --config c3 --no-cpu-baseline --no-extra-legs > $O/bench_c3.json 2> $O/bench_c3.err
-      timeout -k 10 300 python3 bench.py --config c5 --no-cpu-baseline --no-extra-legs > $O/bench_c5.json 2> $O/bench_c5.err ;;
+      timeout -k 10 300 python3 bench.py --config c3 --full --no-cpu-baseline --no-extra-legs > $O/bench_c3.json 2> $O/bench_c3.err
+      timeout -k 10 300 python3 bench.py --config c5 --full --no-cpu-baseline --no-extra-legs > $O/bench_c5.json 2> $O/bench_c5.err ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

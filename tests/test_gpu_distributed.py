@@ -89,7 +89,7 @@ def test_bench_two_ranks_gloo_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1", "--envs", "1024",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -109,7 +109,8 @@ def test_bench_self_launch_two_ranks():
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--steps", "3",
-           "--warmup", "1", "--envs", "1024", "--no-cpu-baseline", "--no-extra-legs", "--no-policy", "--no-pipeline"]
+           "--warmup", "1", "--envs", "1024", "--full", "--no-cpu-baseline", "--no-extra-legs", "--no-policy",
+           "--no-pipeline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -169,7 +170,7 @@ def test_bench_one_rank_rccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "1", "--init-dist", "--dist-backend", "nccl", "--steps", "3", "--warmup", "1", "--envs", "1024",
-           "--no-cpu-baseline", "--no-extra-legs"]
+           "--full", "--no-cpu-baseline", "--no-extra-legs"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
