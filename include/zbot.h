@@ -55,6 +55,10 @@ size_t      zb_config_struct_bytes(void);
 int         zb_state_stride(void);
 int         zb_rand_stride(void);
 const char* zb_last_error(void);
+/* Floor colliders beyond the soles that one substep holds before the overflow
+ * flag (ZB_S_NAN bit 1) is set: 0 where the model has none, 2 with one or two,
+ * 4 with more, with or without the sole pair. Host only. */
+int         zb_bank_cap(const ZbModel* model);
 
 /* Fill `cfg` with the train.py defaults (train.py:1766-1788 + registered
  * components). Host only. */
@@ -73,14 +77,15 @@ void zb_default_config(ZbEnvConfig* cfg);
  * kernels; any other collider set runs a general-collider instantiation with a
  * second bank of 32 contact-row lanes (Jacobian rows in per-env global scratch),
  * which holds, each substep, the first two of the other colliders within reach
- * of the floor. A model with more than two colliders beyond the soles (and no
- * self pair) adds a third bank of floor colliders: the first four within reach.
+ * of the floor. A model with more than two colliders beyond the soles adds a
+ * third bank of floor colliders: the first four within reach (zb_bank_cap).
  * A substep with more within reach than the banks hold sets bit 1 of the state's
  * flag word (ZB_S_NAN; bit 0: non-finite; bit 2: the same, for the current
  * control step only). npair = 1 (the two box soles against each other,
  * geom-geom) holds the pair's contacts in that second bank when the soles are the
- * only colliders, and in a third bank beside the floor colliders' otherwise (the
- * floor colliders beyond the soles then keep the two of the second bank).
+ * only colliders, and otherwise in a bank of its own after the floor colliders'
+ * one or two: the third beside up to two colliders beyond the soles, the fourth
+ * beside more (the pair takes no floor collider's place).
  *
  * Create a handle simulating `n_envs` environments whose global ids are
  * [env_offset, env_offset + n_envs) — RNG streams are keyed by global id, so

@@ -139,7 +139,9 @@ int zb_create(const ZbModel* model, const ZbEnvConfig* cfg, int n_envs, int env_
   if (e == hipSuccess) e = hipMemset(h->itpart, 0, n * sizeof(int32_t));
   h->xg = zb::needs_xg(model);
   /* XG 4: two banks in global scratch per env (the floor selection, the sole pair) */
-  if (e == hipSuccess && h->xg) e = hipMalloc(&h->xj, (n + 1) * ZB_XJ_STRIDE * (h->xg == 4 || h->xg == 5 ? 2 : 1) * sizeof(float));
+  /* one block per contact-row bank beyond the first (zb_engine.hip XJ_STRIDE) */
+  const size_t xj_banks = h->xg == 6 ? 3 : (h->xg == 4 || h->xg == 5) ? 2 : 1;
+  if (e == hipSuccess && h->xg) e = hipMalloc(&h->xj, (size_t)(n + 1) * ZB_XJ_STRIDE * xj_banks * sizeof(float));
   h->nchunk = choose_chunks(n_envs, cfg->n_substeps, zb::step_resident_blocks(device, h->xg, cfg->solver, (cfg->flags & ZB_F_EULERDAMP) ? 1 : 0));
 #if defined(ZB_STAMPS) || defined(ZB_WAVETIME)
   {

@@ -39,7 +39,7 @@
    values whose kernels this unit compiles; the entry points of the first unit hand the others' to the
    second unit's (*_tu_b). Without the defines (diagnostic builds) one unit holds every XG. */
 #ifndef ZB_XG_MASK
-#define ZB_XG_MASK 0x3F
+#define ZB_XG_MASK 0x7F
 #endif
 #ifdef ZB_ENGINE_TU_B
 #define ZB_EP(f) f##_tu_b
@@ -50,7 +50,7 @@
 namespace zb {
 constexpr int XG_MASK = ZB_XG_MASK;
 __host__ __device__ constexpr bool xg_here(int xg) { return ((XG_MASK >> xg) & 1) != 0; }
-#if !defined(ZB_ENGINE_TU_B) && ZB_XG_MASK != 0x3F
+#if !defined(ZB_ENGINE_TU_B) && ZB_XG_MASK != 0x7F
 int step_resident_blocks_tu_b(int device, int xg, int solver, int ed);
 hipError_t launch_step_tu_b(const StepArgs& a, hipStream_t s);
 hipError_t launch_reset_tu_b(const StepArgs& a, hipStream_t s);
@@ -572,9 +572,11 @@ __device__ __forceinline__ gfloat_t* xrows(const EnvL* L) {
 }
 /* XG 4 / 5: the third bank's rows follow the second bank's in the env's block */
 __device__ __forceinline__ gfloat_t* yrows(const EnvL* L) { return xrows(L) + 32 * CAP; }
+/* XG 6: the fourth bank's rows (the sole pair's half rows) follow the third bank's */
+__device__ __forceinline__ gfloat_t* zrows(const EnvL* L) { return xrows(L) + 2 * 32 * CAP; }
 /* floats of StepArgs::xj per env: one [32][CAP] block per extra bank */
 template <int XG>
-constexpr int XJ_STRIDE = ZB_XJ_STRIDE * (XG == 4 || XG == 5 ? 2 : 1);
+constexpr int XJ_STRIDE = ZB_XJ_STRIDE * (XG == 6 ? 3 : XG == 4 || XG == 5 ? 2 : 1);
 __device__ __forceinline__ void set_xrows(EnvL* L, float* base) {
   L->s.xj_lo = (uint32_t)(uint64_t)base;
   L->s.xj_hi = (uint32_t)((uint64_t)base >> 32);
@@ -758,7 +760,8 @@ struct Rows {
   int nrow;
   uint32_t exmask; /* team-uniform: existing contact rows */
   XRow x;          /* second bank (XG kernels only) */
-  XRow y;          /* third bank: the sole pair beside floor colliders (XG 4 only) */
+  XRow y;          /* third bank: the sole pair beside floor colliders (XG 4), floor colliders (XG 5, 6) */
+  XRow z;          /* fourth bank: the sole pair beside two banks of floor colliders (XG 6 only) */
 };
 
 /* 16-byte LDS row access (rows are 12 floats = 48 B, 16-B aligned) */
@@ -1556,6 +1559,9 @@ __device__ __forceinline__ float row_dot_x(const Ctx& c, const Rows& r, int slot
 __device__ __forceinline__ float row_dot_y(const Ctx& c, const Rows& r, int slot) {
   return row_dot(c, (const gfloat_t*)yrows(c.L) + c.l * CAP, r.y.chd, slot);
 }
+__device__ __forceinline__ float row_dot_z(const Ctx& c, const Rows& r, int slot) {
+  return row_dot(c, (const gfloat_t*)zrows(c.L) + c.l * CAP, r.z.chd, slot);
+}
 
 /* row_dot with the lane's row already in registers (jr) */
 __device__ __forceinline__ float row_dot_pre(const Ctx& c, const float jr[CAP], int chd, int slot) {
@@ -1756,22 +1762,51 @@ __device__ __forceinline__ void row_params(PR solref, PS solimp, float pos, floa
    XG 2 compiles cylinders, ellipsoids and meshes), XG 3 the sole pair (the two box soles against each
    other, pair_rows), XG 4 both: the floor colliders in the second bank and the sole pair in a third
    (Rows::y, round 6), XG 5 (models with more than two colliders beyond the soles) floor colliders in
-   the second and third banks: the first four within reach of the floor each substep. XG 0: the two
-   soles alone. */
+   the second and third banks: the first four within reach of the floor each substep. XG 6: XG 5's two
+   floor banks and the sole pair in a fourth (Rows::z), held as XG 4 holds it in the third. XG 0: the
+   two soles alone. */
 template <int XG>
-constexpr bool XFLOOR = XG == 1 || XG == 2 || XG == 4 || XG == 5;
+constexpr bool XFLOOR = XG == 1 || XG == 2 || XG == 4 || XG == 5 || XG == 6;
 template <int XG>
 constexpr bool XPAIR = XG == 3; /* the pair in the second bank */
 template <int XG>
 constexpr bool YPAIR = XG == 4; /* the pair in the third bank */
 template <int XG>
-constexpr bool YFLOOR = XG == 5; /* floor colliders in the third bank too */
+constexpr bool ZPAIR = XG == 6; /* the pair in the fourth bank */
+template <int XG>
+constexpr bool YFLOOR = XG == 5 || XG == 6; /* floor colliders in the third bank too */
 template <int XG>
 constexpr bool YBANK = YPAIR<XG> || YFLOOR<XG>; /* the third bank exists */
 template <int XG>
-constexpr bool XRICH = XG == 2 || XG == 4 || XG == 5; /* cylinder / ellipsoid / mesh rules compiled */
+constexpr bool XRICH = XG == 2 || XG == 4 || XG == 5 || XG == 6; /* cylinder / ellipsoid / mesh rules compiled */
 template <int XG>
-constexpr bool ANYPAIR = XPAIR<XG> || YPAIR<XG>;
+constexpr bool ANYPAIR = XPAIR<XG> || YPAIR<XG> || ZPAIR<XG>;
+/* The bank that holds the sole pair's half rows (ANYPAIR: the second, third or fourth), its Jacobian
+   rows in the env's scratch block, and its static row masks as the two low bits of the result: bits
+   2-3 of the lane's row-mask word where the pair has the second bank (TP_ROWMASK2), else bits 4-5
+   (TP_ROWMASK3). A bank after the first holds either floor colliders or the pair. */
+template <int XG>
+__device__ __forceinline__ XRow& pair_bank(Rows& r) {
+  if constexpr (ZPAIR<XG>) return r.z;
+  else if constexpr (YPAIR<XG>) return r.y;
+  else return r.x;
+}
+template <int XG>
+__device__ __forceinline__ const XRow& pair_bank(const Rows& r) {
+  if constexpr (ZPAIR<XG>) return r.z;
+  else if constexpr (YPAIR<XG>) return r.y;
+  else return r.x;
+}
+template <int XG>
+__device__ __forceinline__ gfloat_t* pair_jrows(const EnvL* L) {
+  if constexpr (ZPAIR<XG>) return zrows(L);
+  else if constexpr (YPAIR<XG>) return yrows(L);
+  else return xrows(L);
+}
+template <int XG>
+__device__ __forceinline__ uint32_t pair_rmb(const Ctx& c) {
+  return XPAIR<XG> ? (c.rmb >> 2) : (c.rmb >> 4);
+}
 
 /* The collider of team lane l in contact-row bank `bank`: geom 2 bank + l / 16 (general colliders), or
    sole l / 16 (the two-sole and sole-pair kernels). gb: its body; false when the model has no such geom. */
@@ -2548,10 +2583,6 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
        usual case: shins and hands off the floor) */
     r.x.any = __ballot(r.x.ex) != 0ull;
     bool yany = false;
-    if constexpr (YPAIR<XG>) {
-      pair_rows(c, s, B, cm, r.y, yrows(c.L) + l * CAP);
-      r.y.any = yany = __ballot(r.y.ex) != 0ull;
-    }
     if constexpr (YFLOOR<XG>) {
       /* XG 5: the third and fourth geoms within reach in the third bank, row masks as the second's */
       contact_rows<XG>(c, s, B, cm, 2, r.y, yrows(c.L) + l * CAP);
@@ -2567,6 +2598,13 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
       }
       r.y.rowmask = rm;
       r.y.any = yany = __ballot(r.y.ex) != 0ull;
+    }
+    if constexpr (YPAIR<XG> || ZPAIR<XG>) {
+      /* the pair's half rows in the bank after the floor colliders' (the third: XG 4, the fourth: XG 6) */
+      XRow& p = pair_bank<XG>(r);
+      pair_rows(c, s, B, cm, p, pair_jrows<XG>(c.L) + l * CAP);
+      p.any = __ballot(p.ex) != 0ull;
+      yany = yany || p.any;
     }
     if (r.x.any || yany) {
       /* the rows just stored are read by other lanes from here on */
@@ -2654,7 +2692,7 @@ __device__ __forceinline__ float eval_one(float jar, float D, float& force, int&
 /* row costs at given jar values (no state change); jx: the second bank's contact row (XG) */
 template <int XG, bool XA = true>
 __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc, float jf_, float jl_, float jx,
-                                           float jy = 0.f) {
+                                           float jy = 0.f, float jz = 0.f) {
   float f;
   int a;
   const float k0 = eval_one(jc, r.D, f, a);
@@ -2674,6 +2712,10 @@ __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc
   if constexpr (YBANK<XG> && XA) {
     const float k4 = eval_one(jy, r.y.D, f, a);
     cost += (r.y.ex && (YFLOOR<XG> || c.l < 16)) ? k4 : 0.f; /* the pair's halves: once */
+  }
+  if constexpr (ZPAIR<XG> && XA) {
+    const float k5 = eval_one(jz, r.z.D, f, a);
+    cost += (r.z.ex && c.l < 16) ? k5 : 0.f; /* the pair's halves: once */
   }
   return cost;
 }
@@ -2777,6 +2819,21 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
       sy1 = tsh(cy, 16 + ddep);
     }
   }
+  float sz0 = 0.f, sz1 = 0.f;
+  if constexpr (ZPAIR<XG> && XA) {
+    /* XG 6: the pair's half rows in the fourth bank */
+    if (r.z.any) {
+      float f5;
+      int a5;
+      const float k5 = eval_one(r.z.jar, r.z.D, f5, a5);
+      cost += (r.z.ex && c.l < 16) ? k5 : 0.f; /* the pair's halves: once */
+      r.z.f = r.z.ex ? f5 : r.z.f;
+      r.z.act = r.z.ex ? a5 : r.z.act;
+      const float cz = colsum16((const gfloat_t*)zrows(c.L) + c.l * CAP, r.z.ex ? r.z.f : 0.f);
+      sz0 = tsh(cz, ddep);
+      sz1 = tsh(cz, 16 + ddep);
+    }
+  }
   /* J'f per dof: a dof adds the column sum at its depth of every geom whose chain holds it */
   const float colsum = colsum16_pre(jr, r.ex ? r.f : 0.f);
   const float so = tsh(colsum, ddep), sx = tsh(colsum, 16 + ddep);
@@ -2795,6 +2852,11 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
       const bool f4 = YFLOOR<XG> ? (r.y.rowmask & 0xFFFFu) != 0u : (c.rmb & 16u) != 0u;
       const bool f5 = YFLOOR<XG> ? (r.y.rowmask >> 16) != 0u : (c.rmb & 32u) != 0u;
       qc += (f4 ? sy0 : 0.f) + (f5 ? sy1 : 0.f);
+    }
+    if constexpr (ZPAIR<XG> && XA) {
+      /* the pair's static row masks (XG 6: its floor banks' masks are this substep's) */
+      const uint32_t pb = pair_rmb<XG>(c);
+      qc += ((pb & 1u) != 0u ? sz0 : 0.f) + ((pb & 2u) != 0u ? sz1 : 0.f);
     }
     if (r.hf) qc += r.ff;
     if (r.anyl && r.hl) qc += r.sl * r.flim;
@@ -3028,6 +3090,11 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
     if constexpr (YPAIR<XG>) jy += xor16f(jy); /* the pair's row: both halves */
     r.y.Jv = jy;
   }
+  if constexpr (ZPAIR<XG> && XA) {
+    float jz = r.z.any ? row_dot_z(c, r, V_TMP) : 0.f;
+    jz += xor16f(jz); /* the pair's row: both halves */
+    r.z.Jv = jz;
+  }
   tsync();
   /* the quadratic's coefficients and the slope/curvature at alpha = 0 in one reduction:
      d1(0) = search . grad (the gradient update_constraint left for the current active
@@ -3043,6 +3110,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   if constexpr (XG && XA) g20 += (r.x.ex && r.x.act && xprim) ? r.x.D * r.x.Jv * r.x.Jv : 0.f;
   if constexpr (YBANK<XG> && XA)
     g20 += (r.y.ex && r.y.act && (YFLOOR<XG> || c.l < 16)) ? r.y.D * r.y.Jv * r.y.Jv : 0.f;
+  if constexpr (ZPAIR<XG> && XA) g20 += (r.z.ex && r.z.act && c.l < 16) ? r.z.D * r.z.Jv * r.z.Jv : 0.f;
   float cc[4] = {isd ? search * (Ma - fs) : 0.f, isd ? search * Mv : 0.f, isd ? search * grad : 0.f, g20};
   tsum_n<4>(cc);
   const float c1 = cc[0], c2 = cc[1];
@@ -3061,6 +3129,8 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   const float DXJ = (XG && XA && r.x.ex && xprim) ? r.x.D * r.x.Jv : 0.f, DXJ2 = (XG && XA) ? DXJ * r.x.Jv : 0.f;
   const float DYJ = (YBANK<XG> && XA && r.y.ex && (YFLOOR<XG> || c.l < 16)) ? r.y.D * r.y.Jv : 0.f,
               DYJ2 = (YBANK<XG> && XA) ? DYJ * r.y.Jv : 0.f;
+  const float DZJ = (ZPAIR<XG> && XA && r.z.ex && c.l < 16) ? r.z.D * r.z.Jv : 0.f,
+              DZJ2 = (ZPAIR<XG> && XA) ? DZJ * r.z.Jv : 0.f;
   float d1 = cc[2], d2 = c2 + cc[3];
   if (!(d1 < 0.f) || !(d2 > 0.f)) return 0.f;
   const float gtol = cfg->ls_tolerance * (-d1);
@@ -3104,6 +3174,11 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
           g1 += DYJ * fminf(xy, 0.f);
           g2 += xy < 0.f ? DYJ2 : 0.f;
         }
+        if constexpr (ZPAIR<XG>) {
+          const float xz = r.z.jar + alpha * r.z.Jv;
+          g1 += DZJ * fminf(xz, 0.f);
+          g2 += xz < 0.f ? DZJ2 : 0.f;
+        }
       }
       float gg[2] = {g1, g2};
       tsum_n<2>(gg);
@@ -3128,24 +3203,25 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
 
 /* H p for the sole-pair kernels' Newton direction (hsolve_pair): M p, the floor rows' and dof rows'
    D J J' p over the current active set (the terms of the factored tree Hessian H_t, hessian_factor:
-   the soles' bank and, XG 4, the floor colliders' bank), plus the pair's active rows' D u u' p (u: the
-   row over both limbs, held as two half rows: the second bank in XG 3, the third in XG 4). */
+   the soles' bank and the floor colliders' one (XG 4) or two (XG 6) banks), plus the pair's active rows'
+   D u u' p (u: the row over both limbs, held as two half rows in pair_bank: the second bank in XG 3, the
+   third in XG 4, the fourth in XG 6). */
 template <int XG>
 __device__ __forceinline__ float hmul_pair(const Ctx& c, const Rows& r, const float jr[CAP], float p) {
   const int ddep = vopq(c.ddep);
   float jv, unused_;
   const float Mp = mul_m_dot(c, r, jr, p, V_TMP, jv, -1, unused_);
-  const XRow& pr = YPAIR<XG> ? r.y : r.x;
-  float jp = row_dot(c, (const gfloat_t*)(YPAIR<XG> ? yrows(c.L) : xrows(c.L)) + c.l * CAP, pr.chd, V_TMP);
+  const XRow& pr = pair_bank<XG>(r);
+  float jp = row_dot(c, (const gfloat_t*)pair_jrows<XG>(c.L) + c.l * CAP, pr.chd, V_TMP);
   jp += xor16f(jp);
   const float w0 = (r.ex && r.act) ? r.D * jv : 0.f;
   const float wp = (pr.ex && pr.act) ? pr.D * jp : 0.f;
   const float cs0 = colsum16_pre(jr, w0);
-  const float cs1 = colsum16((const gfloat_t*)(YPAIR<XG> ? yrows(c.L) : xrows(c.L)) + c.l * CAP, wp);
+  const float cs1 = colsum16((const gfloat_t*)pair_jrows<XG>(c.L) + c.l * CAP, wp);
   const float so = tsh(cs0, ddep), sx = tsh(cs0, 16 + ddep), s2 = tsh(cs1, ddep), s3 = tsh(cs1, 16 + ddep);
   float s4 = 0.f, s5 = 0.f;
-  if constexpr (YPAIR<XG>) {
-    /* XG 4: the floor colliders' bank is part of H_t */
+  if constexpr (XFLOOR<XG>) {
+    /* XG 4, 6: the floor colliders' bank is part of H_t */
     if (r.x.any) {
       const float jf = row_dot_x(c, r, V_TMP);
       const float wf = (r.x.ex && r.x.act) ? r.x.D * jf : 0.f;
@@ -3154,16 +3230,31 @@ __device__ __forceinline__ float hmul_pair(const Ctx& c, const Rows& r, const fl
       s5 = tsh(cs2, 16 + ddep);
     }
   }
+  float s6 = 0.f, s7 = 0.f;
+  if constexpr (YFLOOR<XG>) {
+    /* XG 6: and the second floor bank */
+    if (r.y.any) {
+      const float jf = row_dot_y(c, r, V_TMP);
+      const float wf = (r.y.ex && r.y.act) ? r.y.D * jf : 0.f;
+      const float cs3 = colsum16((const gfloat_t*)yrows(c.L) + c.l * CAP, wf);
+      s6 = tsh(cs3, ddep);
+      s7 = tsh(cs3, 16 + ddep);
+    }
+  }
   float y = 0.f;
   if (c.l < NV) {
     const bool f0 = (c.rmb & 1u) != 0u, f1 = (c.rmb & 2u) != 0u;
-    /* the pair's static row masks: rmb bits 2-3 (XG 3) or 4-5 (XG 4) */
-    const uint32_t pb = YPAIR<XG> ? (c.rmb >> 4) : (c.rmb >> 2);
+    /* the pair's static row masks: rmb bits 2-3 (XG 3) or 4-5 (XG 4, 6) */
+    const uint32_t pb = pair_rmb<XG>(c);
     const bool f2 = (pb & 1u) != 0u, f3 = (pb & 2u) != 0u;
     y = Mp + (f0 ? so : 0.f) + (f1 ? sx : 0.f) + (f2 ? s2 : 0.f) + (f3 ? s3 : 0.f);
-    if constexpr (YPAIR<XG>) {
+    if constexpr (XFLOOR<XG>) {
       const bool f4 = (r.x.rowmask & 0xFFFFu) != 0u, f5 = (r.x.rowmask >> 16) != 0u;
       y += (f4 ? s4 : 0.f) + (f5 ? s5 : 0.f);
+    }
+    if constexpr (YFLOOR<XG>) {
+      const bool f6 = (r.y.rowmask & 0xFFFFu) != 0u, f7 = (r.y.rowmask >> 16) != 0u;
+      y += (f6 ? s6 : 0.f) + (f7 ? s7 : 0.f);
     }
     if (r.hf && r.actf) y += r.Df * p;
     if (r.anyl && r.hl && r.actl) y += r.Dl * p;
@@ -3183,7 +3274,7 @@ template <int XG>
 __device__ __forceinline__ float hsolve_pair(const Ctx& c, const Rows& r, const float jr[CAP], float g, float Dinv) {
   const bool isd = c.l < NV;
   float z = solve_ldl(c, g, Dinv);
-  const XRow& pr = YPAIR<XG> ? r.y : r.x;
+  const XRow& pr = pair_bank<XG>(r);
   if (team_ballot(pr.ex && pr.act) == 0u) return z;
   float x = 0.f, rr = isd ? g : 0.f, p = isd ? z : 0.f;
   float dd[2] = {isd ? rr * z : 0.f, isd ? g * g : 0.f};
@@ -3251,9 +3342,20 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
       jsy -= r.y.aref;
     }
   }
+  float jwz = 0.f, jsz = 0.f;
+  if constexpr (ZPAIR<XG> && XA) {
+    if (r.z.any) {
+      jwz = row_dot_z(c, r, V_TMP);
+      jsz = row_dot_z(c, r, V_TMP2);
+      jwz += xor16f(jwz); /* the pair's row: both halves */
+      jsz += xor16f(jsz);
+      jwz -= r.z.aref;
+      jsz -= r.z.aref;
+    }
+  }
   tsync();
-  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy),
-                  rows_cost<XG, XA>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy)};
+  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy, jwz),
+                  rows_cost<XG, XA>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy, jsz)};
   tsum_n<2>(cws);
   const float cw = cws[0], cs = cws[1];
   if (cw > cs) {
@@ -3262,10 +3364,12 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     r.jar = js;
     r.x.jar = jsx;
     r.y.jar = jsy;
+    if constexpr (ZPAIR<XG>) r.z.jar = jsz;
   } else {
     r.jar = jw;
     r.x.jar = jwx;
     r.y.jar = jwy;
+    if constexpr (ZPAIR<XG>) r.z.jar = jwz;
   }
   STAMP(S_WARM);
   r.jf = x - r.af;
@@ -3292,6 +3396,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     r.jar += alpha * r.Jv;
     if constexpr (XG && XA) r.x.jar += alpha * r.x.Jv;
     if constexpr (YBANK<XG> && XA) r.y.jar += alpha * r.y.Jv;
+    if constexpr (ZPAIR<XG> && XA) r.z.jar += alpha * r.z.Jv;
     r.jf += alpha * search;
     if (r.anyl) r.jl += alpha * (r.sl * search);
     float oldcost = cost;
@@ -3380,9 +3485,20 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
       jsy -= r.y.aref;
     }
   }
+  float jwz = 0.f, jsz = 0.f;
+  if constexpr (ZPAIR<XG> && XA) {
+    if (r.z.any) {
+      jwz = row_dot_z(c, r, V_TMP);
+      jsz = row_dot_z(c, r, V_TMP2);
+      jwz += xor16f(jwz); /* the pair's row: both halves */
+      jsz += xor16f(jsz);
+      jwz -= r.z.aref;
+      jsz -= r.z.aref;
+    }
+  }
   tsync();
-  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy),
-                  rows_cost<XG, XA>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy)};
+  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy, jwz),
+                  rows_cost<XG, XA>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy, jsz)};
   tsum_n<2>(cws);
   if (cws[0] > cws[1]) {
     x = qs;
@@ -3390,10 +3506,12 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     r.jar = js;
     r.x.jar = jsx;
     r.y.jar = jsy;
+    if constexpr (ZPAIR<XG>) r.z.jar = jsz;
   } else {
     r.jar = jw;
     r.x.jar = jwx;
     r.y.jar = jwy;
+    if constexpr (ZPAIR<XG>) r.z.jar = jwz;
   }
   STAMP(S_WARM);
   r.jf = x - r.af;
@@ -3418,6 +3536,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     r.jar += alpha * r.Jv;
     if constexpr (XG && XA) r.x.jar += alpha * r.x.Jv;
     if constexpr (YBANK<XG> && XA) r.y.jar += alpha * r.y.Jv;
+    if constexpr (ZPAIR<XG> && XA) r.z.jar += alpha * r.z.Jv;
     r.jf += alpha * search;
     if (r.anyl) r.jl += alpha * (r.sl * search);
     const float oldcost = cost, gold = grad, mgold = mg;
@@ -3535,7 +3654,8 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   /* constraints */
   make_constraints<XG>(c, s, ls, B, cm, r);
   STAMP(S_CON);
-  int nrows = tmaxi(r.nrow + (XG ? r.x.nrow : 0) + (YBANK<XG> ? r.y.nrow : 0) + (r.hf || r.hl ? 1 : 0));
+  int nrows = tmaxi(r.nrow + (XG ? r.x.nrow : 0) + (YBANK<XG> ? r.y.nrow : 0) + (ZPAIR<XG> ? r.z.nrow : 0) +
+                     (r.hf || r.hl ? 1 : 0));
   float qacc;
   /* entered by the whole wave when either env has rows (the full Hessian
      build runs on the matrix cores and needs every lane); an env without
@@ -3552,7 +3672,7 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
       return SOLVER == ZB_SOLVER_CG ? solve_cg<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft)
                                     : solve_newton<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
     };
-    const bool xa = XG != 0 && (r.x.any || (YBANK<XG> && r.y.any)); /* wave-uniform */
+    const bool xa = XG != 0 && (r.x.any || (YBANK<XG> && r.y.any) || (ZPAIR<XG> && r.z.any)); /* wave-uniform */
     const float qn = xa ? solve(BoolC<true>{}) : solve(BoolC<false>{});
     if (nrows > 0) {
       qacc = qn;
@@ -3591,17 +3711,23 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   } else if (YFLOOR<XG> && r.y.any) {
     (void)contact_point<XG>(c, s, B, 2, ypos, ydir, cmu);
   }
+  float zpos[3], zdir[3];
+  if constexpr (ZPAIR<XG>) {
+    if (r.z.any) pair_dir(zpos, zdir);
+  }
   const int rgeom = c.l >> 4;
   float tch0 = 0.f, tch1 = 0.f;
-  for (int g = 0; g < (YBANK<XG> ? 3 * NGEOM : XG ? 2 * NGEOM : NGEOM); g++) {
-    /* geom g: bank g / 2, lanes 16 (g % 2) .. + 15 (XG 4: bank 2 = the pair's halves) */
-    const bool b1 = XG && g >= NGEOM && g < 2 * NGEOM, b2 = YBANK<XG> && g >= 2 * NGEOM;
+  for (int g = 0; g < (ZPAIR<XG> ? 4 * NGEOM : YBANK<XG> ? 3 * NGEOM : XG ? 2 * NGEOM : NGEOM); g++) {
+    /* geom g: bank g / 2, lanes 16 (g % 2) .. + 15 (XG 4: bank 2, XG 6: bank 3 = the pair's halves) */
+    const bool b1 = XG && g >= NGEOM && g < 2 * NGEOM, b2 = YBANK<XG> && g >= 2 * NGEOM && g < 3 * NGEOM,
+               b3 = ZPAIR<XG> && g >= 3 * NGEOM;
     if (b1 && !r.x.any) continue; /* wave-uniform */
     if (b2 && !r.y.any) continue;
-    const bool mine = (b2 ? r.y.ex : b1 ? r.x.ex : r.ex) && rgeom == (g & 1);
-    const float rf = b2 ? r.y.f : b1 ? r.x.f : r.f;
-    const float* pp = b2 ? ypos : b1 ? xpos : cpos;
-    const float* dd = b2 ? ydir : b1 ? xdir : cdir;
+    if (b3 && !r.z.any) continue;
+    const bool mine = (b3 ? r.z.ex : b2 ? r.y.ex : b1 ? r.x.ex : r.ex) && rgeom == (g & 1);
+    const float rf = b3 ? r.z.f : b2 ? r.y.f : b1 ? r.x.f : r.f;
+    const float* pp = b3 ? zpos : b2 ? ypos : b1 ? xpos : cpos;
+    const float* dd = b3 ? zdir : b2 ? ydir : b1 ? xdir : cdir;
     float F[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
     float fn = 0.f;
     if (mine) {
@@ -3616,7 +3742,8 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
     float fnt = ex7[6];
     /* the pair's halves: g = 2 geom2's body (+F), g = 3 geom1's (-F, in xdir); each foot's touch
        sensor takes the pair's normal force (its geom is in the contact) */
-    const int gg = (YFLOOR<XG> && b2) ? c.L->ysel[g - 2 * NGEOM]
+    const int gg = b3 ? m->pair_geom[g == 3 * NGEOM ? 1 : 0]
+                   : (YFLOOR<XG> && b2) ? c.L->ysel[g - 2 * NGEOM]
                    : b2 ? m->pair_geom[g == 2 * NGEOM ? 1 : 0]
                    : (XPAIR<XG> && b1) ? m->pair_geom[g == NGEOM ? 1 : 0]
                    : (XFLOOR<XG> && b1) ? c.L->s.xsel[g - NGEOM] : g;
@@ -4515,11 +4642,12 @@ __global__ __launch_bounds__(64) void debug_forward_kernel(StepArgs a) {
     for (int k = 0; k < 6; k++) d[ZB_DBG_CVEL + 6 * l + k] = B.cv[k];
   }
   int nefc = (int)tsum((float)((r.ex ? 1 : 0) + (XG && r.x.ex && (!XPAIR<XG> || l < 16) ? 1 : 0) +
-                               (YBANK<XG> && r.y.ex && (YFLOOR<XG> || l < 16) ? 1 : 0) + (r.hf ? 1 : 0) +
+                               (YBANK<XG> && r.y.ex && (YFLOOR<XG> || l < 16) ? 1 : 0) +
+                               (ZPAIR<XG> && r.z.ex && l < 16 ? 1 : 0) + (r.hf ? 1 : 0) +
                                (r.hl ? 1 : 0)));
   if (l == 0) {
     d[ZB_DBG_MISC + 0] = (float)nefc;
-    d[ZB_DBG_MISC + 1] = (float)((r.nrow + (XG ? r.x.nrow / (XPAIR<XG> ? 2 : 1) : 0) + (YBANK<XG> ? r.y.nrow / (YPAIR<XG> ? 2 : 1) : 0)) / 4);
+    d[ZB_DBG_MISC + 1] = (float)((r.nrow + (XG ? r.x.nrow / (XPAIR<XG> ? 2 : 1) : 0) + (YBANK<XG> ? r.y.nrow / (YPAIR<XG> ? 2 : 1) : 0) + (ZPAIR<XG> ? r.z.nrow / 2 : 0)) / 4);
     d[ZB_DBG_MISC + 2] = sen.touch[0];
     d[ZB_DBG_MISC + 3] = sen.touch[1];
     for (int k = 0; k < 4; k++) d[ZB_DBG_MISC + 4 + k] = sen.fq[k];
@@ -4550,7 +4678,8 @@ __global__ __launch_bounds__(64) void debug_forward_kernel(StepArgs a) {
 }
 
 /* the kernel instantiation for a handle: solver x collider set (zb_host.cpp needs_xg: 0 two soles,
-   1 / 2 general floor colliders, 3 the sole pair, 4 both) x implicit damping (ZB_F_EULERDAMP, step kernel
+   1 / 2 general floor colliders, 3 the sole pair, 4 both, 5 two banks of floor colliders, 6 those and
+   the sole pair) x implicit damping (ZB_F_EULERDAMP, step kernel
    only). f(S, X, D) is called with std::integral_constant values. */
 template <typename F>
 __host__ void with_variant(int solver, int xg, int ed, F&& f) {
@@ -4558,6 +4687,7 @@ __host__ void with_variant(int solver, int xg, int ed, F&& f) {
   auto by_xg = [&](auto S, auto D) {
     switch (xg) {
       /* only this unit's XG values are instantiated (ZB_XG_MASK); the entry points hand the others off */
+      case 6: if constexpr (xg_here(6)) f(S, integral_constant<int, 6>{}, D); break;
       case 5: if constexpr (xg_here(5)) f(S, integral_constant<int, 5>{}, D); break;
       case 4: if constexpr (xg_here(4)) f(S, integral_constant<int, 4>{}, D); break;
       case 3: if constexpr (xg_here(3)) f(S, integral_constant<int, 3>{}, D); break;

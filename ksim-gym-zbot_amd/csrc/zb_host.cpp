@@ -104,9 +104,10 @@ int check_model(const ZbModel* m) {
                 m->nskip_pair);
   if (m->nbody > 32 || m->nv > 32 || m->nq > ZB_MAX_QPOS)
     return fail(ZB_EMODEL, "model too large for a 32-lane team (nbody=%d nv=%d nq=%d)", m->nbody, m->nv, m->nq);
-  /* colliders: two banks of 32 contact-row lanes, 16 rows (4 contacts x 4 pyramid edges) per geom; the
+  /* colliders: banks of 32 contact-row lanes, 16 rows (4 contacts x 4 pyramid edges) per geom; the
      first bank holds geoms 0-1 (the soles), the second the first two others within reach of the floor
-     each substep (zb_engine.hip select_bank2) */
+     each substep (zb_engine.hip select_bank2), a third the next two where the model has more than two
+     others; the sole pair's half rows take the bank after the floor colliders' (needs_xg, bank_cap) */
   if (m->ngeom < 1 || m->ngeom > ZB_MAX_GEOM)
     return fail(ZB_EMODEL, "ngeom=%d: 1 to %d floor colliders", m->ngeom, ZB_MAX_GEOM);
   for (int g = 0; g < m->ngeom; g++) {
@@ -134,7 +135,7 @@ int check_model(const ZbModel* m) {
   if (m->npair == 1) {
     /* the sole pair (zb_engine.hip pair_rows): the two box soles (geoms 0 and 1, the touch sensors'),
        on two different limbs (its contact rows are one half-row per limb chain); with other floor
-       colliders beside them its rows take a bank of their own (XG 4) */
+       colliders beside them its rows take a bank of their own (XG 4, XG 6) */
     const int g1 = m->pair_geom[0], g2 = m->pair_geom[1];
     if (m->ngeom < 2 || !((g1 == 0 && g2 == 1) || (g1 == 1 && g2 == 0)))
       return fail(ZB_EMODEL, "the sole pair collides the two soles, geoms 0 and 1 (ngeom=%d, pair %d-%d)",
@@ -196,8 +197,9 @@ int check_model(const ZbModel* m) {
 
 int needs_xg(const ZbModel* m) {
   /* the sole pair: alone with the soles (XG 3, the second bank holds the pair's rows), or beside other
-     floor colliders (XG 4: the floor bank and a third bank for the pair's rows) */
-  if (m->npair > 0) return m->ngeom > 2 ? 4 : 3;
+     floor colliders: up to two of them in one floor bank and a third bank for the pair's rows (XG 4),
+     more than two in two floor banks, as XG 5 holds them, and a fourth bank for the pair's rows (XG 6) */
+  if (m->npair > 0) return m->ngeom == 2 ? 3 : m->ngeom <= 4 ? 4 : 6;
   /* ZB_FORCE_XG=1 (profiling only): the two-sole model on the general-collider instantiation, whose
      second bank then stays empty, to time that kernel's overhead on the headline's work */
   const char* fx = getenv("ZB_FORCE_XG");
@@ -210,6 +212,13 @@ int needs_xg(const ZbModel* m) {
     if (m->geom_type[g] == ZB_GEOM_CYLINDER || m->geom_type[g] == ZB_GEOM_ELLIPSOID || m->geom_type[g] == ZB_GEOM_MESH)
       return 2;
   return 1;
+}
+
+int bank_cap(const ZbModel* m) {
+  /* the floor banks beyond the soles' hold two colliders each: one bank up to two such colliders
+     (needs_xg 1, 2, 4), two banks for more (5, 6); exactly the soles: none */
+  if (m->ngeom <= 2) return 0;
+  return m->ngeom <= 4 ? 2 : 4;
 }
 
 int check_cfg(const ZbEnvConfig* c) {
@@ -318,6 +327,8 @@ using zb::fail;
 extern "C" {
 
 const char* zb_last_error(void) { return zb::g_err.c_str(); }
+
+int zb_bank_cap(const ZbModel* model) { return model ? zb::bank_cap(model) : 0; }
 
 void zb_default_config(ZbEnvConfig* c) {
   if (!c) return;

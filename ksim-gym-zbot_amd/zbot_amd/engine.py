@@ -54,6 +54,8 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.zb_rand_stride.restype = C.c_int
     L.zb_last_error.restype = C.c_char_p
     L.zb_default_config.argtypes = [C.POINTER(cs.ZbEnvConfig)]
+    L.zb_bank_cap.argtypes = [C.POINTER(cs.ZbModel)]
+    L.zb_bank_cap.restype = C.c_int
     L.zb_create.argtypes = [C.POINTER(cs.ZbModel), C.POINTER(cs.ZbEnvConfig), C.c_int, C.c_int, C.c_int, C.c_uint64,
                             C.POINTER(vp)]
     L.zb_destroy.argtypes = [vp]
@@ -113,6 +115,15 @@ def _ptr(t) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def bank_cap(model) -> int:
+    """Floor colliders beyond the soles that one substep holds before the overflow flag
+    (state_flags()["bank_overflow"]) is set: 0 where the model has none, 2 with one or two, 4 with
+    more, with or without the sole pair (zb_bank_cap; needs no GPU). `model`: a compiled model or
+    its ZbModel."""
+    cm = model.cmodel if hasattr(model, "cmodel") else model
+    return int(load_library().zb_bank_cap(C.byref(cm)))
+
+
 DBG_STRIDE = 1760
 DBG = dict(qM=0, bias=1024, qacc_smooth=1056, qacc=1088, xpos=1120, cinert=1216, cvel=1536, misc=1728)
 
@@ -121,7 +132,8 @@ def state_flags(state) -> dict:
     """The sticky diagnostic flags of a [n, ZB_STATE_STRIDE] state (get_state()), as boolean [n]
     tensors (include/zbot_layout.h ZB_S_NAN): `nonfinite` - the env's state went non-finite;
     `bank_overflow` - in some substep more colliders beyond the soles were within reach of the floor
-    than the contact-row banks hold (four; two beside the sole pair), and the extra ones' contacts were
+    than the contact-row banks hold (bank_cap(model): four, two for a model with at most two such
+    colliders), and the extra ones' contacts were
     not simulated (zb_engine.hip select_bank2).
     Both are sticky for the life of the env's state row (resets keep them; set_state() can clear
     them). `bank_overflow_step`: the same overflow in the last control step alone (the kernel clears

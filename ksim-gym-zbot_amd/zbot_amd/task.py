@@ -213,18 +213,18 @@ class ZbotWalkingEnv:
 
     def check_bank_overflow(self, state=None) -> int:
         """Envs whose second contact-row bank overflowed at some substep (more colliders beyond the soles
-        within reach of the floor than the banks hold: four, two beside the sole pair; the extra ones' contacts were not simulated: zb_engine.hip
-        select_bank2, engine.state_flags). Warns once per env object the first time any env has; called
-        by update_curriculum() after every rollout. Returns the count."""
-        from .engine import state_flags  # noqa: PLC0415
+        within reach of the floor than the banks hold, engine.bank_cap(model); the extra ones' contacts
+        were not simulated: zb_engine.hip select_bank2, engine.state_flags). Warns once per env object
+        the first time any env has; called by update_curriculum() after every rollout. Returns the count."""
+        from .engine import bank_cap, state_flags  # noqa: PLC0415
 
         n = int(state_flags(self.engine.get_state() if state is None else state)["bank_overflow"].sum().item())
         if n and not getattr(self, "_overflow_warned", False):
             import warnings  # noqa: PLC0415
 
             warnings.warn(f"{n} env(s) had more colliders beyond the soles within reach of the floor in one "
-                          "substep than the contact-row banks hold; the extra contacts were not simulated (DESIGN.md §4j)", RuntimeWarning,
-                          stacklevel=2)
+                          f"substep than the contact-row banks hold ({bank_cap(self.model)}); the extra contacts "
+                          "were not simulated (DESIGN.md §4j)", RuntimeWarning, stacklevel=2)
             self._overflow_warned = True
         return n
 
