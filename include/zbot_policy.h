@@ -105,6 +105,60 @@ int zb_policy_actor(ZbPolicy* p, const float* obs, int T, int n, float* carry, c
 int zb_policy_critic(ZbPolicy* p, const float* obs, int T, int n, float* carry, const uint8_t* reset, float* value,
                      void* stream);
 
+/*
+ * ---- Training: activation-saving forward and the vector-Jacobian product ----
+ *
+ * The learner's half of PPO (get_ppo_variables differentiates through the GRU scan,
+ * train.py:1683-1729). None of these entry points changes what the inference entry points
+ * compute. All pointers are device pointers; every call is asynchronous on `stream`, allocates
+ * nothing, and returns an error code instead of launching on a bad argument (a scratch buffer
+ * smaller than zb_policy_train_scratch_words is one). They always run the 32-env block layout.
+ *
+ *   reset[t][e] zeroes the carry before step t as in inference, and the gradient through time is
+ *   cut at the same place (train.py:1719-1723). carry0 [n][D][H] is read-only data: it gets no
+ *   gradient. The actor's trailing 20 mean offsets (JOINT_BIASES, train.py:963) are constants:
+ *   their grad entries are written as 0.
+ *
+ * Scratch (fp32 words, K = T n rows): what the training forward saves per (t, env) — the input
+ * projection, and per layer the old carry, r, z, n, W_hn h + b_n and the output h'; the actor's
+ * 300 raw head outputs — then what backward adds — per layer (da_r, da_z, da_n, da_n r), the
+ * gradient of the input projection's output and of the raw head outputs — and the split-K
+ * partials of the parameter gradient. Nothing is recomputed in backward but the mixture head.
+ *
+ * Reduction order of the parameter gradient (two identical calls return identical bits; no
+ * floating-point atomics): the K rows, in (t, env) order, are cut into C = min(32, ceil(K / 512))
+ * chunks of ceil(K / C) rows rounded up to a multiple of 16. A chunk's rows are taken in sub-chains
+ * of 512 rows: for every weight gradient element each sub-chain is one matrix-core chain from 0
+ * over its rows in row order (v_mfma_f32_16x16x4_f32: 4 rows a step), and the chunk's partial is
+ * the sub-chain sums added in order, ((s0 + s1) + s2) + ... A bias gradient element is one fp64
+ * matrix-core chain over the whole chunk (v_mfma_f64_16x16x4_f64), rounded to fp32 once. The C
+ * chunk partials p[0..31] (p[c] = 0 for c >= C) are then combined by the fixed tree
+ * p[c] += p[c + s] for s = 16, 8, 4, 2, 1.
+ */
+
+/* fp32 words of scratch a (kind, T, n) training forward writes and its backward reads (0 on a bad argument) */
+size_t zb_policy_train_scratch_words(int kind, int T, int n);
+
+/* Replace the handle's parameters from a DEVICE buffer in the natural layout (zb_policy_param_count
+ * floats): repacked on the GPU into the forward's fragment order and backward's transposed packs. */
+int zb_policy_set_params(ZbPolicy* p, const float* params, size_t n_params, void* stream);
+
+/* Training forward: the arithmetic and bits of zb_policy_actor(mode = ZB_POL_EVAL) / zb_policy_critic
+ * over T steps, with carry0 [n][D][H] read-only and the activations saved to scratch. */
+int zb_policy_actor_train(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                          const float* actions, float* log_prob, float* scratch, size_t scratch_words, void* stream);
+int zb_policy_critic_train(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                           float* value, float* scratch, size_t scratch_words, void* stream);
+
+/* VJP after the training forward of the same arguments and scratch:
+ * grad [param_count] (natural layout, overwritten) = d(sum d_log_prob * log_prob) / d params
+ * (d_log_prob [T][n][20]; critic: d_value [T][n]). */
+int zb_policy_actor_backward(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                             const float* actions, const float* d_log_prob, float* scratch, size_t scratch_words,
+                             float* grad, void* stream);
+int zb_policy_critic_backward(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                              const float* d_value, float* scratch, size_t scratch_words, float* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

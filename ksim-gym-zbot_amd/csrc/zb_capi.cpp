@@ -438,6 +438,8 @@ struct ZbPolicy {
   int device;
   float* wpack;
   float* bias;
+  float* wpack_t; /* backward's transposed packs: per layer W_ih^T, W_hh^T; the actor's W_out^T */
+  size_t wpack_words, wpack_t_words, bias_words;
   int layout; /* ZB_POL_LAYOUT_* */
   int persistent; /* block layout: one launch per call over all T steps */
 };
@@ -465,6 +467,14 @@ static void pack_b(const float* W, int N, int K, std::vector<float>& out) {
         }
 }
 
+/* the same fragments of W^T, W [K][N] natural: backward's B operand of dgi W (zb_policy_train.hip) */
+static void pack_bt(const float* W, int K, int N, std::vector<float>& out) {
+  std::vector<float> wt((size_t)N * K);
+  for (int k = 0; k < K; k++)
+    for (int r = 0; r < N; r++) wt[(size_t)r * K + k] = W[(size_t)k * N + r];
+  pack_b(wt.data(), N, K, out);
+}
+
 int zb_policy_create(int kind, const float* params, size_t n_params, int device, ZbPolicy** out) {
   if (!out || !params) return fail(ZB_EARG, "zb_policy_create: null argument");
   *out = nullptr;
@@ -472,7 +482,7 @@ int zb_policy_create(int kind, const float* params, size_t n_params, int device,
   const size_t need = zb_policy_param_count(kind);
   if (n_params != need) return fail(ZB_EARG, "zb_policy_create: %zu parameters, expected %zu", n_params, need);
   const int H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH, I = pol_in(kind), O = pol_out(kind);
-  std::vector<float> wp, bias;
+  std::vector<float> wp, bias, wt;
   const float* p = params;
   pack_b(p, H, I, wp); /* input_proj.weight */
   p += (size_t)H * I;
@@ -480,8 +490,10 @@ int zb_policy_create(int kind, const float* params, size_t n_params, int device,
   p += H;
   for (int l = 0; l < D; l++) {
     pack_b(p, 3 * H, H, wp); /* weight_ih */
+    pack_bt(p, 3 * H, H, wt);
     p += (size_t)3 * H * H;
     pack_b(p, 3 * H, H, wp); /* weight_hh */
+    pack_bt(p, 3 * H, H, wt);
     p += (size_t)3 * H * H;
     bias.insert(bias.end(), p, p + 4 * H); /* bias [3H], bias_n [H] */
     p += 4 * H;
@@ -492,6 +504,7 @@ int zb_policy_create(int kind, const float* params, size_t n_params, int device,
   p += O;
   if (kind == ZB_POL_ACTOR) {
     pack_b(wout, O, H, wp);
+    pack_bt(wout, O, H, wt);
     bias.insert(bias.end(), p, p + ZB_POL_JOINTS); /* mean offsets (JOINT_BIASES) */
   } else {
     bias.insert(bias.end(), wout, wout + H); /* value head, natural layout */
@@ -510,8 +523,12 @@ int zb_policy_create(int kind, const float* params, size_t n_params, int device,
   h->device = device;
   h->wpack = nullptr;
   h->bias = nullptr;
+  h->wpack_t = nullptr;
+  h->wpack_words = wp.size(), h->wpack_t_words = wt.size(), h->bias_words = bias.size();
   hipError_t e = hipMalloc(&h->wpack, wp.size() * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&h->bias, bias.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc(&h->wpack_t, wt.size() * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(h->wpack_t, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(h->bias, bias.data(), bias.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
@@ -527,6 +544,7 @@ int zb_policy_destroy(ZbPolicy* h) {
   (void)hipSetDevice(h->device);
   if (h->wpack) (void)hipFree(h->wpack);
   if (h->bias) (void)hipFree(h->bias);
+  if (h->wpack_t) (void)hipFree(h->wpack_t);
   delete h;
   return ZB_OK;
 }
@@ -603,6 +621,129 @@ int zb_policy_critic(ZbPolicy* p, const float* obs, int T, int n, float* carry, 
                      void* stream) {
   return policy_run(p, ZB_POL_CRITIC, obs, T, n, carry, reset, ZB_POL_SAMPLE, 0, 0, 0, nullptr, nullptr, value,
                     stream);
+}
+
+/* ---- training: activation-saving forward and VJP (include/zbot_policy.h, zb_policy_train.hip) ---- */
+
+size_t zb_policy_train_scratch_words(int kind, int T, int n) {
+  if ((kind != ZB_POL_ACTOR && kind != ZB_POL_CRITIC) || T <= 0 || n <= 0) return 0;
+  return zb::train_layout(kind, T, n).total;
+}
+
+int zb_policy_set_params(ZbPolicy* h, const float* params, size_t n_params, void* stream) {
+  if (!h || !params) return fail(ZB_EARG, "zb_policy_set_params: null argument");
+  const size_t need = zb_policy_param_count(h->kind);
+  if (n_params != need) return fail(ZB_EARG, "zb_policy_set_params: %zu parameters, expected %zu", n_params, need);
+  int cur = -1;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->device) HIPCHK(hipSetDevice(h->device));
+  hipError_t e = zb::launch_policy_pack(h->kind, params, h->wpack, h->wpack_t, h->bias, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_policy_set_params: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+/* shared argument checks of the four training entry points; 1 = nothing to do */
+static int train_check(ZbPolicy* h, int kind, const float* obs, int T, int n, const float* carry0, const void* a,
+                       const void* b, const float* scratch, size_t scratch_words, const char* what) {
+  if (!h) return fail(ZB_EARG, "%s: null policy handle", what);
+  if (h->kind != kind)
+    return fail(ZB_EARG, "%s: policy handle is a%s", what, h->kind == ZB_POL_ACTOR ? "n actor" : " critic");
+  if (T < 0 || n < 0) return fail(ZB_EARG, "%s: bad size (T=%d n=%d)", what, T, n);
+  if (T == 0 || n == 0) return 1;
+  if ((unsigned long long)T * (unsigned long long)n > 0x7fffffffULL)
+    return fail(ZB_EARG, "%s: T n = %llu rows exceed 2^31 - 1", what, (unsigned long long)T * n);
+  if (!obs || !carry0 || !a || !b || !scratch) return fail(ZB_EARG, "%s: null pointer", what);
+  if ((uintptr_t)carry0 % 16) return fail(ZB_EARG, "%s: carry0 must be 16-byte aligned", what);
+  const size_t need = zb::train_layout(kind, T, n).total;
+  if (scratch_words < need)
+    return fail(ZB_EARG, "%s: scratch of %zu words, (T=%d, n=%d) needs %zu", what, scratch_words, T, n, need);
+  int cur = -1;
+  HIPCHK(hipGetDevice(&cur));
+  if (cur != h->device) HIPCHK(hipSetDevice(h->device));
+  return ZB_OK;
+}
+
+static int train_forward(ZbPolicy* h, int kind, const float* obs, int T, int n, const float* carry0,
+                         const uint8_t* reset, const float* actions, float* log_prob, float* value, float* scratch,
+                         size_t scratch_words, void* stream) {
+  const char* what = kind == ZB_POL_ACTOR ? "zb_policy_actor_train" : "zb_policy_critic_train";
+  const int rc = train_check(h, kind, obs, T, n, carry0, kind == ZB_POL_ACTOR ? (const void*)actions : (const void*)value,
+                             kind == ZB_POL_ACTOR ? (const void*)log_prob : (const void*)value, scratch, scratch_words,
+                             what);
+  if (rc != ZB_OK) return rc == 1 ? ZB_OK : rc;
+  zb::PolicyArgs a;
+  memset(&a, 0, sizeof a);
+  a.obs = obs;
+  a.carry = const_cast<float*>(carry0); /* read-only in the SAVE kernels */
+  a.reset = reset;
+  a.n = n;
+  a.mode = ZB_POL_EVAL;
+  a.actions = const_cast<float*>(actions); /* EVAL reads them */
+  a.log_prob = log_prob;
+  a.value = value;
+  a.wpack = h->wpack;
+  a.bias = h->bias;
+  a.layout = ZB_POL_LAYOUT_BLOCK;
+  a.T = T;
+  a.save = scratch;
+  hipError_t e = zb::launch_policy(kind, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+  return ZB_OK;
+}
+
+static int train_backward(ZbPolicy* h, int kind, const float* obs, int T, int n, const float* carry0,
+                          const uint8_t* reset, const float* actions, const float* dout, float* scratch,
+                          size_t scratch_words, float* grad, void* stream) {
+  const char* what = kind == ZB_POL_ACTOR ? "zb_policy_actor_backward" : "zb_policy_critic_backward";
+  if (!grad) return fail(ZB_EARG, "%s: null grad", what);
+  const int rc = train_check(h, kind, obs, T, n, carry0, kind == ZB_POL_ACTOR ? (const void*)actions : (const void*)dout,
+                             dout, scratch, scratch_words, what);
+  if (rc == 1) {
+    hipError_t e = hipMemsetAsync(grad, 0, zb_policy_param_count(kind) * sizeof(float), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+    return ZB_OK;
+  }
+  if (rc != ZB_OK) return rc;
+  zb::PolicyBwdArgs a;
+  memset(&a, 0, sizeof a);
+  a.obs = obs;
+  a.reset = reset;
+  a.actions = actions;
+  a.dout = dout;
+  a.scratch = scratch;
+  a.grad = grad;
+  a.wpack_t = h->wpack_t;
+  a.bias = h->bias;
+  a.T = T;
+  a.n = n;
+  hipError_t e = zb::launch_policy_backward(kind, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
+  return ZB_OK;
+}
+
+int zb_policy_actor_train(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                          const float* actions, float* log_prob, float* scratch, size_t scratch_words, void* stream) {
+  return train_forward(p, ZB_POL_ACTOR, obs, T, n, carry0, reset, actions, log_prob, nullptr, scratch, scratch_words,
+                       stream);
+}
+
+int zb_policy_critic_train(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                           float* value, float* scratch, size_t scratch_words, void* stream) {
+  return train_forward(p, ZB_POL_CRITIC, obs, T, n, carry0, reset, nullptr, nullptr, value, scratch, scratch_words,
+                       stream);
+}
+
+int zb_policy_actor_backward(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                             const float* actions, const float* d_log_prob, float* scratch, size_t scratch_words,
+                             float* grad, void* stream) {
+  return train_backward(p, ZB_POL_ACTOR, obs, T, n, carry0, reset, actions, d_log_prob, scratch, scratch_words, grad,
+                        stream);
+}
+
+int zb_policy_critic_backward(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
+                              const float* d_value, float* scratch, size_t scratch_words, float* grad, void* stream) {
+  return train_backward(p, ZB_POL_CRITIC, obs, T, n, carry0, reset, nullptr, d_value, scratch, scratch_words, grad,
+                        stream);
 }
 
 #if defined(ZB_STAMPS) || defined(ZB_WAVETIME)

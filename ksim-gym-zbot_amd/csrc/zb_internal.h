@@ -109,8 +109,75 @@ struct PolicyArgs {
   int layout;             /* ZB_POL_LAYOUT_BLOCK / ZB_POL_LAYOUT_WAVE */
   int T;                  /* block layout: steps run by one persistent launch (obs / reset / outputs
                              advance by one [n] step each; carry in registers between steps) */
+  float* save;            /* training forward (zb_policy_*_train): scratch base, else null; carry is then
+                             read-only (carry0) */
 };
 hipError_t launch_policy(int kind, const PolicyArgs& a, hipStream_t s);
+
+/* Training scratch (include/zbot_policy.h): planes of K = T n rows in (t, env) order, offsets in
+   fp32 words. Per-layer planes are [layer][K][cols]. */
+#define ZB_TR_RAW_LD 304     /* row stride of the actor's raw head outputs (300) and their gradient */
+#define ZB_TR_DG_LD 512      /* (da_r, da_z, da_n, da_n r) of one layer: dgi = cols 0..383, dgh = 0..255 + 384..511 */
+#define ZB_TR_MAX_CHUNKS 32
+struct TrainLayout {
+  size_t K;
+  size_t x0;    /* [K][H] input projection output */
+  size_t hp;    /* [D][K][H] carry each layer read (after the reset) */
+  size_t r, z, nn, hn, ho; /* [D][K][H] gates, W_hn h + b_n, layer output */
+  size_t raw;   /* [K][304] actor */
+  size_t dg;    /* [D][K][512] */
+  size_t dx0;   /* [K][H] */
+  size_t draw;  /* [K][304] actor */
+  size_t part;  /* [chunks][param_count] */
+  size_t total;
+  int chunks;   /* split-K chunks of the parameter gradient */
+  int chunk_rows;
+};
+__host__ __device__ static inline size_t policy_param_count(int kind) {
+  const size_t H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH;
+  const size_t I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN, O = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_OUT : 1;
+  return H * I + H + D * (6 * H * H + 4 * H) + O * H + O + (kind == ZB_POL_ACTOR ? ZB_POL_JOINTS : 0);
+}
+__host__ __device__ static inline TrainLayout train_layout(int kind, int T, int n) {
+  TrainLayout L;
+  const size_t H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH, K = (size_t)T * (size_t)n;
+  const size_t act = kind == ZB_POL_ACTOR ? K * ZB_TR_RAW_LD : 0;
+  size_t o = 0;
+  L.K = K;
+  L.x0 = o, o += K * H;
+  L.hp = o, o += D * K * H;
+  L.r = o, o += D * K * H;
+  L.z = o, o += D * K * H;
+  L.nn = o, o += D * K * H;
+  L.hn = o, o += D * K * H;
+  L.ho = o, o += D * K * H;
+  L.raw = o, o += act;
+  L.dg = o, o += D * K * ZB_TR_DG_LD;
+  L.dx0 = o, o += K * H;
+  L.draw = o, o += act;
+  size_t c = (K + 511) / 512;
+  c = c < 1 ? 1 : (c > ZB_TR_MAX_CHUNKS ? ZB_TR_MAX_CHUNKS : c);
+  L.chunks = (int)c;
+  L.chunk_rows = (int)(((K + c - 1) / c + 15) / 16 * 16);
+  L.part = o, o += c * policy_param_count(kind);
+  L.total = o;
+  return L;
+}
+
+struct PolicyBwdArgs {
+  const float* obs;       /* [T][n][I] */
+  const uint8_t* reset;   /* [T][n] or null */
+  const float* actions;   /* [T][n][20] (actor) */
+  const float* dout;      /* d_log_prob [T][n][20] (actor) / d_value [T][n] (critic) */
+  float* scratch;
+  float* grad;            /* [param_count] */
+  const float* wpack_t;   /* transposed fragment packs: per layer W_ih^T, W_hh^T; then W_out^T (actor) */
+  const float* bias;      /* as PolicyArgs::bias */
+  int T, n;
+};
+hipError_t launch_policy_backward(int kind, const PolicyBwdArgs& a, hipStream_t s);
+/* device repack of natural-layout parameters into wpack / wpack_t / bias */
+hipError_t launch_policy_pack(int kind, const float* params, float* wpack, float* wpack_t, float* bias, hipStream_t s);
 
 hipError_t launch_normalize(const float* gae, float* adv, long long count, const double* mom, double total,
                             float eps, hipStream_t s);

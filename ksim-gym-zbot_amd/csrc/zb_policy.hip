@@ -104,7 +104,10 @@ __device__ __forceinline__ void tile_gemm(const float* xs, const float4* wp, int
    for both spilled in the one-step launches too (the critic 121 VGPRs; actor 19), round 6 splits it
    (one-step actor 0.111 -> 0.107 ms, critic 0.134 -> 0.111 ms at 8192 envs, no spills, the same bits;
    profiles/r06_p11_policy_ab.log). */
-template <int KIN, int NOUT, bool ACTOR, bool PERSIST>
+/* SAVE: the training forward (zb_policy_*_train): the same arithmetic, with the carry read
+   from carry0 and never written back, and what backward needs stored per (t, env) row of the scratch
+   planes (zb_internal.h TrainLayout). Only stores are added, so the bits are those of SAVE = false. */
+template <int KIN, int NOUT, bool ACTOR, bool PERSIST, bool SAVE = false>
 __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) {
 #pragma clang fp contract(off)
   constexpr int KPAD = (KIN + 15) / 16 * 16;
@@ -145,6 +148,12 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
   if (a0.log_prob) a.log_prob = a0.log_prob + (size_t)t * a0.n * NJ;
   if (a0.value) a.value = a0.value + (size_t)t * a0.n;
   const bool last = t == TT - 1;
+  [[maybe_unused]] TrainLayout tl;
+  [[maybe_unused]] size_t row0 = 0; /* scratch row of this block's env 0 at step t */
+  if constexpr (SAVE) {
+    tl = train_layout(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, a0.T, a0.n);
+    row0 = (size_t)t * a0.n + e0;
+  }
 
   constexpr int CPT = M * (H / 4) / NTHR;
   static_assert(CPT * NTHR == M * (H / 4), "carry float4s per thread");
@@ -218,7 +227,14 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
 #pragma unroll
     for (int et = 0; et < NET; ++et)
 #pragma unroll
-      for (int v = 0; v < 4; ++v) sx[0][unit * LDA + crow(et, v, lane)] = acc[et][v] + bu;
+      for (int v = 0; v < 4; ++v) {
+        const float xv = acc[et][v] + bu;
+        sx[0][unit * LDA + crow(et, v, lane)] = xv;
+        if constexpr (SAVE) {
+          const int e = crow(et, v, lane);
+          if (e0 + e < a.n) a0.save[tl.x0 + (row0 + e) * H + unit] = xv;
+        }
+      }
   }
 
   /* 3. GRU stack (train.py:945-948) */
@@ -319,7 +335,19 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
         const float ho = sh[unit * LDA + e];
         const float hv = nn + z * (ho - nn);
         xo[unit * LDA + e] = hv;
-        if (last && e0 + e < a.n) a.carry[((size_t)(e0 + e) * D + l) * H + unit] = hv;
+        if constexpr (SAVE) {
+          if (e0 + e < a.n) {
+            const size_t i = ((size_t)l * tl.K + row0 + e) * H + unit;
+            a0.save[tl.hp + i] = ho;
+            a0.save[tl.r + i] = r;
+            a0.save[tl.z + i] = z;
+            a0.save[tl.nn + i] = nn;
+            a0.save[tl.hn + i] = ha[2][et][v] + bnh;
+            a0.save[tl.ho + i] = hv;
+          }
+        } else {
+          if (last && e0 + e < a.n) a.carry[((size_t)(e0 + e) * D + l) * H + unit] = hv;
+        }
         if (TT > 1) {
 #pragma unroll
           for (int k = 0; k < D; ++k) hreg[k][et][v] = l == k ? hv : hreg[k][et][v];
@@ -345,7 +373,13 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
 #pragma unroll
         for (int et = 0; et < NET; ++et)
 #pragma unroll
-          for (int v = 0; v < 4; ++v) su[crow(et, v, lane) * OUTS + c] = acc[et][v] + bc;
+          for (int v = 0; v < 4; ++v) {
+            const int e = crow(et, v, lane);
+            su[e * OUTS + c] = acc[et][v] + bc;
+            if constexpr (SAVE) {
+              if (e0 + e < a.n) a0.save[tl.raw + (row0 + e) * ZB_TR_RAW_LD + c] = acc[et][v] + bc;
+            }
+          }
       }
     }
     __syncthreads();
@@ -626,6 +660,15 @@ hipError_t launch_policy(int kind, const PolicyArgs& a, hipStream_t s) {
   }
   const int nblk = (a.n + pol::M - 1) / pol::M;
   const bool persist = a.T > 1;
+  if (a.save) {
+    if (kind == ZB_POL_ACTOR)
+      hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, ZB_POL_ACTOR_OUT, true, true, true>), dim3(nblk),
+                         dim3(pol::NTHR), 0, s, a);
+    else
+      hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_CRITIC_IN, 1, false, true, true>), dim3(nblk), dim3(pol::NTHR),
+                         0, s, a);
+    return hipGetLastError();
+  }
   if (kind == ZB_POL_ACTOR) {
     if (persist)
       hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, ZB_POL_ACTOR_OUT, true, true>), dim3(nblk),

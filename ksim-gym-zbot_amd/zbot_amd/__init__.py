@@ -4,6 +4,10 @@ The compute path is libzbot_hip.so (HIP, gfx950) behind the C ABI in
 include/zbot.h; this package compiles the robot descriptor, loads the library
 through ctypes and exposes a ksim-shaped engine/task interface over PyTorch
 device tensors.
+
+Submodules that need torch are imported on demand: `policy` (the GRU actor /
+critic and PolicyRollout), `ppo` (GAE, value targets, advantages) and
+`learner` (gradients through both networks, the PPO loss and update).
 """
 
 from . import cstructs

@@ -95,6 +95,17 @@ def load_library(path: str | None = None) -> C.CDLL:
     for f in ("zb_policy_create", "zb_policy_destroy", "zb_policy_actor", "zb_policy_critic", "zb_policy_set_layout",
               "zb_policy_set_persistent"):
         getattr(L, f).restype = C.c_int
+    # training forward and VJP of the same networks (include/zbot_policy.h "Training")
+    L.zb_policy_train_scratch_words.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.zb_policy_train_scratch_words.restype = C.c_size_t
+    L.zb_policy_set_params.argtypes = [vp, vp, C.c_size_t, vp]
+    L.zb_policy_actor_train.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.zb_policy_critic_train.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp]
+    L.zb_policy_actor_backward.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    L.zb_policy_critic_backward.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_size_t, vp, vp]
+    for f in ("zb_policy_set_params", "zb_policy_actor_train", "zb_policy_critic_train", "zb_policy_actor_backward",
+              "zb_policy_critic_backward"):
+        getattr(L, f).restype = C.c_int
     if L.zb_abi_version() != ABI_VERSION:
         raise ZbError(f"{lp}: ABI version {L.zb_abi_version()}, this binding speaks {ABI_VERSION}: rebuild it")
     if L.zb_model_struct_bytes() != C.sizeof(cs.ZbModel):

@@ -4,6 +4,8 @@ Mirrors train.py's Model (Actor :885-967, Critic :970-1023, get_model
 :1604-1614) and ZbotWalkingTask.run_actor / run_critic / sample_action
 (:1616-1681, :1737-1763). The networks run in libzbot_hip.so on the f32
 matrix cores (include/zbot_policy.h); there is no PyTorch or CPU fallback.
+Training them (the activation-saving forward, the backward pass and a torch
+autograd wrapper over both) is zbot_amd.learner.
 
     actor = GruPolicy(ACTOR, init_params(ACTOR, seed=0))
     carry = actor.initial_carry(n)                          # get_initial_model_carry
@@ -94,6 +96,7 @@ class GruPolicy:
         if p.size != param_count(kind):
             raise ZbError(f"{p.size} parameters, expected {param_count(kind)}")
         self.params = p
+        self._params_dev = None  # device copy of the natural-layout parameters (params_tensor)
         h = C.c_void_p()
         _check(self.L.zb_policy_create(kind, p.ctypes.data_as(C.POINTER(C.c_float)), p.size, device, C.byref(h)))
         self.h = h
@@ -109,6 +112,95 @@ class GruPolicy:
         """Block layout: a call over T steps as one persistent launch with the carry in registers
         (default), or one launch per step; bit-identical (include/zbot_policy.h)."""
         _check(self.L.zb_policy_set_persistent(self.h, 1 if on else 0))
+
+    def set_params(self, params) -> None:
+        """Replace the handle's parameters from a device tensor in the natural layout
+        (zb_policy_set_params: repacked on the GPU, asynchronous on the current stream). Every later
+        launch of this handle, PolicyRollout's included, runs the new weights."""
+        torch = self.torch
+        p = self._dev(params.detach().reshape(-1), torch.float32)
+        if p.numel() != param_count(self.kind):
+            raise ZbError(f"{p.numel()} parameters, expected {param_count(self.kind)}")
+        _check(self.L.zb_policy_set_params(self.h, p.data_ptr(), p.numel(), self._stream()))
+        self._params_dev = p.clone()
+        self.params = None  # the host copy is stale: params_tensor() is the record
+
+    def params_tensor(self):
+        """The handle's parameters in the natural layout, as a float32 device tensor (a copy)."""
+        if self._params_dev is None:
+            self._params_dev = self.torch.from_numpy(self.params).to(self.device)
+        return self._params_dev.clone()
+
+    def train_scratch_words(self, T: int, n: int) -> int:
+        """fp32 words of scratch a (T, n) training forward writes and its backward reads."""
+        return int(self.L.zb_policy_train_scratch_words(self.kind, int(T), int(n)))
+
+    def _train_args(self, obs, carry0, reset, scratch):
+        torch = self.torch
+        o = self._dev(obs, torch.float32)
+        if o.dim() != 3 or o.shape[2] != self.I:
+            raise ZbError(f"training observations must be [T, n, {self.I}], got {list(o.shape)}")
+        T, n, _ = o.shape
+        self._check_carry(carry0, n)
+        r = None if reset is None else self._dev(reset.reshape(T, n), torch.uint8)
+        if scratch is None:
+            scratch = torch.empty(self.train_scratch_words(T, n), dtype=torch.float32, device=self.device)
+        elif scratch.dtype != torch.float32 or scratch.device != self.device or not scratch.is_contiguous():
+            raise ZbError(f"scratch must be a contiguous float32 tensor on {self.device}")
+        return o, T, n, r, scratch
+
+    def actor_train(self, obs, actions, carry0, reset=None, scratch=None):
+        """Training forward of the actor (zb_policy_actor_train): obs [T, n, 50], actions [T, n, 20],
+        carry0 [n, 5, 128] read-only -> (log_prob [T, n, 20] with the bits of actor(mode=EVAL), scratch).
+        `scratch` holds the saved activations for actor_backward."""
+        if self.kind != ACTOR:
+            raise ZbError("actor_train() on a critic handle")
+        o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
+        a = self._dev(actions.reshape(T, n, JOINTS), self.torch.float32)
+        lp = self.torch.empty(T, n, JOINTS, dtype=self.torch.float32, device=self.device)
+        _check(self.L.zb_policy_actor_train(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
+                                            None if r is None else r.data_ptr(), a.data_ptr(), lp.data_ptr(),
+                                            scratch.data_ptr(), scratch.numel(), self._stream()))
+        return lp, scratch
+
+    def critic_train(self, obs, carry0, reset=None, scratch=None):
+        """Training forward of the critic (zb_policy_critic_train) -> (value [T, n], scratch)."""
+        if self.kind != CRITIC:
+            raise ZbError("critic_train() on an actor handle")
+        o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
+        v = self.torch.empty(T, n, dtype=self.torch.float32, device=self.device)
+        _check(self.L.zb_policy_critic_train(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
+                                             None if r is None else r.data_ptr(), v.data_ptr(), scratch.data_ptr(),
+                                             scratch.numel(), self._stream()))
+        return v, scratch
+
+    def actor_backward(self, obs, actions, carry0, reset, d_log_prob, scratch, grad=None):
+        """VJP of actor_train (zb_policy_actor_backward), after it, on the same arguments and scratch:
+        grad [param_count] = d(sum d_log_prob * log_prob) / d params, natural layout."""
+        if self.kind != ACTOR:
+            raise ZbError("actor_backward() on a critic handle")
+        torch = self.torch
+        o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
+        a = self._dev(actions.reshape(T, n, JOINTS), torch.float32)
+        d = self._dev(d_log_prob.reshape(T, n, JOINTS), torch.float32)
+        g = self._out(grad, (param_count(self.kind),), torch.float32)
+        _check(self.L.zb_policy_actor_backward(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
+                                               None if r is None else r.data_ptr(), a.data_ptr(), d.data_ptr(),
+                                               scratch.data_ptr(), scratch.numel(), g.data_ptr(), self._stream()))
+        return g
+
+    def critic_backward(self, obs, carry0, reset, d_value, scratch, grad=None):
+        """VJP of critic_train (zb_policy_critic_backward): grad = d(sum d_value * value) / d params."""
+        if self.kind != CRITIC:
+            raise ZbError("critic_backward() on an actor handle")
+        torch = self.torch
+        o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
+        d = self._dev(d_value.reshape(T, n), torch.float32)
+        g = self._out(grad, (param_count(self.kind),), torch.float32)
+        _check(self.L.zb_policy_critic_backward(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
+                                                None if r is None else r.data_ptr(), d.data_ptr(), scratch.data_ptr(),
+                                                scratch.numel(), g.data_ptr(), self._stream()))
+        return g
 
     def __del__(self):
         h = getattr(self, "h", None)
