@@ -401,6 +401,13 @@ __device__ __forceinline__ float keepf(float v) {
   asm volatile("" : "+v"(v));
   return v;
 }
+/* a product rounded where it stands: the compiler may not contract it into the add that takes it
+   next. `p ? a * b : 0` gave that for free (the select sat between the product and the add); where
+   the mask went because the masked lanes hold exact zeros, this keeps the sum's bits. */
+__device__ __forceinline__ float rounded(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
 /* bitmask over the team's lanes of predicate p */
 __device__ __forceinline__ uint32_t team_ballot(bool p) { return (uint32_t)(__ballot(p) >> (threadIdx.x & 32)); }
 /* An opaque copy of a per-lane constant: stops the compiler from hoisting
@@ -1331,6 +1338,8 @@ __device__ __forceinline__ float load_mrow(const Ctx& c, float X[CAP]) {
  * Q, g in L[lane][0..11] (CG reads no factor row past this point), U in Hs[lane][0..5] (CG builds no
  * Hessian; Hs shares memory with sub[], so the caller runs this after the smooth phase's last subtree
  * sum, rne_project, and the sensors' first one comes after the solver). */
+/* GN: a root lane's own g slot holds -1 (below), which takes six selects out of every solve_pre */
+template <bool GN = true>
 __device__ __forceinline__ void solve_prep(const Ctx& c) {
   EnvL* L = c.L;
   const bool isroot = c.l < NROOT, ischain = c.chd >= 0;
@@ -1390,6 +1399,16 @@ __device__ __forceinline__ void solve_prep(const Ctx& c) {
       g[e] += wm[e] * wmp;
     }
   }
+  /* a root lane e holds -1 in its own slot g[e] (its g is zero: p = -1 makes every wmp zero), so
+     that solve_pre's sr_e = sum over lanes of -g[e] * b takes b_e(root) from the same product: the
+     root lane adds -(-1) * b = b exactly, every other lane -(g[e] * b) as before. Where g[e] * b is
+     a zero its sign may differ from that of 0 - g[e] * b; a sum of zeros of either sign with any
+     non-zero term is the same value, and an all-zero sr_e enters x only as U * sr_e added to other
+     terms: no output divides by it or reads its sign. */
+  if constexpr (GN) {
+#pragma unroll
+    for (int e = 0; e < RMAX; e++) g[e] = (isroot && c.l == e) ? -1.f : g[e];
+  }
   tsync(); /* every lane's reads of the factor rows and of u are done */
   *reinterpret_cast<v4f*>(&L->L[lr][0]) = v4f{Q[0], Q[1], Q[2], Q[3]};
   *reinterpret_cast<v4f*>(&L->L[lr][4]) = v4f{Q[4], Q[5], g[0], g[1]};
@@ -1402,6 +1421,7 @@ __device__ __forceinline__ void solve_prep(const Ctx& c) {
 
 /* x <- M^-1 x with solve_prep's per-lane data (CG): the chain gather and the root sums of b in
    flight together, then x_p = sum_k Q(p, k) b_k + sum_e U(p, e) sr_e (solve_prep) */
+template <bool GN = true>
 __device__ __forceinline__ float solve_pre(const Ctx& c, float x) {
   EnvL* L = c.L;
   const int lr = c.l & 31;
@@ -1416,7 +1436,8 @@ __device__ __forceinline__ float solve_pre(const Ctx& c, float x) {
   for (int k = 0; k < NLIMBLV; k++) bk[k] = tsh(x, chd + k);
   float sr[RMAX];
 #pragma unroll
-  for (int e = 0; e < RMAX; e++) sr[e] = (c.l == e ? x : 0.f) - qg[NLIMBLV + e] * x;
+  for (int e = 0; e < RMAX; e++) /* GN: root lane e holds g[e] = -1 (solve_prep) */
+    sr[e] = GN ? rounded(-(qg[NLIMBLV + e] * x)) : (c.l == e ? x : 0.f) - qg[NLIMBLV + e] * x;
   tsum_n<RMAX>(sr);
   float y = 0.f;
 #pragma unroll
@@ -1507,6 +1528,8 @@ __device__ __forceinline__ float solve_ldl(const Ctx& c, float x, float Dinv) {
 }
 
 /* y = M x (M rows in LDS), x in dof lanes; uses vec[slot] */
+/* XS (solve_cg's copies): one select on x instead of one per product of the root sums */
+template <bool XS = false>
 __device__ __forceinline__ float mul_m(const Ctx& c, float x, int slot) {
   EnvL* L = c.L;
   const int j = c.l;
@@ -1527,9 +1550,13 @@ __device__ __forceinline__ float mul_m(const Ctx& c, float x, int slot) {
     /* root lanes: the limb dofs' M(k, root i) = mrow[i], one transposing reduction
        (the deeper root dofs come with the row product, from the row padding) */
     static_assert(RMAX == 6, "reduce6_lane");
+    /* XS: one select on x instead of one per product (as solve_ldl's xs): a lane off the chains
+       adds mrow[i] * 0, an exact zero for its finite row */
+    const float xs = ischain ? x : 0.f;
     float si[RMAX];
 #pragma unroll
-    for (int i = 0; i < RMAX; i++) si[i] = (ischain && i < nroot) ? mrow[i] * x : 0.f;
+    for (int i = 0; i < RMAX; i++)
+      si[i] = XS ? (i < nroot ? rounded(mrow[i] * xs) : 0.f) : ((ischain && i < nroot) ? mrow[i] * x : 0.f);
     const float sr = reduce6_lane(si); /* root lane j: sum j */
     if (j < nroot) y += sr;
   }
@@ -1578,6 +1605,7 @@ __device__ __forceinline__ float row_dot_pre(const Ctx& c, const float jr[CAP], 
  * call): the row loads go out with mul_m's ancestor gather instead of after its reduction and
  * exchange point. jr: the lane's contact-row Jacobian, loaded once per solve. Bit-identical to
  * mul_m followed by row_dot. */
+template <bool XS = false>
 __device__ __forceinline__ float mul_m_dot(const Ctx& c, const Rows& r, const float jr[CAP], float x, int slot, float& jv,
                                            int slot2, float& jv2) {
   EnvL* L = c.L;
@@ -1597,9 +1625,11 @@ __device__ __forceinline__ float mul_m_dot(const Ctx& c, const Rows& r, const fl
   for (int e = 0; e < CAP; e++) y += mrow[e] * vv[e];
   if (nroot > 0) {
     static_assert(RMAX == 6, "reduce6_lane");
+    const float xs = ischain ? x : 0.f; /* as mul_m */
     float si[RMAX];
 #pragma unroll
-    for (int i = 0; i < RMAX; i++) si[i] = (ischain && i < nroot) ? mrow[i] * x : 0.f;
+    for (int i = 0; i < RMAX; i++)
+      si[i] = XS ? (i < nroot ? rounded(mrow[i] * xs) : 0.f) : ((ischain && i < nroot) ? mrow[i] * x : 0.f);
     const float sr = reduce6_lane(si);
     if (j < nroot) y += sr;
   }
@@ -2761,25 +2791,47 @@ __device__ __forceinline__ float colsum16(JP Jrow, float fr) {
    the Newton loop's other per-iteration sums in one tsum_n) */
 /* HS: the rows' force and active D are also stored in LDS for the Newton Hessian (hessian_factor,
    jdj_mfma); CG builds no Hessian and skips the stores */
-template <int XG, bool XA = true, bool HS = true>
+/* ZL: solve_cg's copies. The caller's qacc, qs, fs and Ma are exact zeros on the lanes past the dofs,
+   whose share of the Gauss cost then needs no mask; the Newton kernels keep the masked forms (their
+   direction is not shown to be zero there, and their code stays what it was) */
+template <int XG, bool XA = true, bool HS = true, bool ZL = false>
 __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, const float jr[CAP], float qacc,
                                                        float qs, float fs, float Ma, float& grad) {
   const int ddep = vopq(c.ddep);
   EnvL* L = c.L;
   float cost = 0.f;
-  if (c.l < NV) cost += 0.5f * (Ma - fs) * (qacc - qs);
+  if constexpr (ZL) cost = rounded(0.5f * (Ma - fs) * (qacc - qs));
+  else if (c.l < NV) cost += 0.5f * (Ma - fs) * (qacc - qs);
   {
-    /* all four row kinds evaluated, results kept only for rows that exist */
+    /* all four row kinds evaluated, results kept only for rows that exist. In solve_cg's copies (ZL)
+       the first bank's contact row and the friction-loss row need no `exists` select for that:
+       - a contact row that does not exist has D = 0 and aref = 0 (contact_rows) and a zero J row
+         (bank 0's rows are stored in every substep, zero without a contact), so its jar is 0 at the
+         warm start and after every step (J qacc and J search are sums of zeros): eval_one then gives
+         force 0, inactive, cost 0, the values contact_rows left in r.f and r.act;
+       - a dof without friction loss has fl = Df = Rf = 0 (make_constraints): eval_fric's zones meet
+         at R fl = 0, so every finite jf is saturated: inactive (actf stays 0), force and cost a
+         zero of either sign. r.ff is read under r.hf only, and a zero of either sign added to the
+         cost changes no sum. */
     float f0, f1;
     int a0, a1;
     const float k0 = eval_one(r.jar, r.D, f0, a0);
     const float k1 = eval_fric(r.jf, r.Df, r.Rf, r.fl, f1, a1);
-    cost += r.ex ? k0 : 0.f;
-    cost += r.hf ? k1 : 0.f;
-    r.f = r.ex ? f0 : r.f;
-    r.act = r.ex ? a0 : r.act;
-    r.ff = r.hf ? f1 : r.ff;
-    r.actf = r.hf ? a1 : r.actf;
+    if constexpr (ZL) {
+      cost += k0;
+      cost += k1;
+      r.f = f0;
+      r.act = a0;
+      r.ff = f1;
+      r.actf = a1;
+    } else {
+      cost += r.ex ? k0 : 0.f;
+      cost += r.hf ? k1 : 0.f;
+      r.f = r.ex ? f0 : r.f;
+      r.act = r.ex ? a0 : r.act;
+      r.ff = r.hf ? f1 : r.ff;
+      r.actf = r.hf ? a1 : r.actf;
+    }
     if (r.anyl) {
       float f2;
       int a2;
@@ -2835,7 +2887,7 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     }
   }
   /* J'f per dof: a dof adds the column sum at its depth of every geom whose chain holds it */
-  const float colsum = colsum16_pre(jr, r.ex ? r.f : 0.f);
+  const float colsum = colsum16_pre(jr, (ZL || r.ex) ? r.f : 0.f); /* ZL: 0 for a row that does not exist (above) */
   const float so = tsh(colsum, ddep), sx = tsh(colsum, 16 + ddep);
   tsync();
   float qc = 0.f;
@@ -2864,10 +2916,10 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
   grad = Ma - fs - qc;
   return cost;
 }
-template <int XG, bool XA = true, bool HS = true>
+template <int XG, bool XA = true, bool HS = true, bool ZL = false>
 __device__ __forceinline__ float update_constraint(const Ctx& c, Rows& r, const float jr[CAP], float qacc, float qs,
                                                   float fs, float Ma, float& grad) {
-  return tsum(update_constraint_lane<XG, XA, HS>(c, r, jr, qacc, qs, fs, Ma, grad));
+  return tsum(update_constraint_lane<XG, XA, HS, ZL>(c, r, jr, qacc, qs, fs, Ma, grad));
 }
 
 /* G_f = sum_{r in foot f} D_r J_r J_r' (depth-indexed 12x12) for both feet of
@@ -3071,15 +3123,17 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
   return full ? factor_ldl<true>(c, H, Hd, L->Hs) : factor_ldl<false>(c, H, Hd, L->Hs);
 }
 
-/* exact line search along `search`; returns alpha (team-uniform) and Mv/Jv */
-template <int XG, bool XA = true>
+/* exact line search along `search`; returns alpha (team-uniform) and Mv/Jv.
+   ZL: search, Ma, fs and grad are exact zeros on the lanes past the dofs (solve_cg): their products
+   are zeros without a mask */
+template <int XG, bool XA = true, bool ZL = false>
 __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float jr[CAP], float search, float Ma, float fs,
                                              float grad, float& Mv) {
   CP cfg = c.cfg;
   EnvL* L = c.L;
   /* leaves search in vec[V_TMP]; J rows are zero where no contact: no branch around the loads */
   float unused_;
-  Mv = mul_m_dot(c, r, jr, search, V_TMP, r.Jv, -1, unused_);
+  Mv = mul_m_dot<ZL>(c, r, jr, search, V_TMP, r.Jv, -1, unused_);
   if constexpr (XG && XA) {
     float jx = r.x.any ? row_dot_x(c, r, V_TMP) : 0.f;
     if constexpr (XPAIR<XG>) jx += xor16f(jx); /* the pair's row: both halves */
@@ -3099,7 +3153,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   /* the quadratic's coefficients and the slope/curvature at alpha = 0 in one reduction:
      d1(0) = search . grad (the gradient update_constraint left for the current active
      set), d2(0) = c2 + sum of D (J search)^2 over the rows active now */
-  const bool isd = c.l < NV;
+  const bool isd = ZL || c.l < NV;
   const float jv0 = isd ? search : 0.f;
   float g20 = (r.ex && r.act) ? r.D * r.Jv * r.Jv : 0.f;
   g20 += (r.hf && r.actf) ? r.Df * jv0 * jv0 : 0.f;
@@ -3112,6 +3166,10 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
     g20 += (r.y.ex && r.y.act && (YFLOOR<XG> || c.l < 16)) ? r.y.D * r.y.Jv * r.y.Jv : 0.f;
   if constexpr (ZPAIR<XG> && XA) g20 += (r.z.ex && r.z.act && c.l < 16) ? r.z.D * r.z.Jv * r.z.Jv : 0.f;
   float cc[4] = {isd ? search * (Ma - fs) : 0.f, isd ? search * Mv : 0.f, isd ? search * grad : 0.f, g20};
+  if constexpr (ZL) {
+#pragma unroll
+    for (int k = 0; k < 3; k++) cc[k] = rounded(cc[k]);
+  }
   tsum_n<4>(cc);
   const float c1 = cc[0], c2 = cc[1];
   /* per-row constants of the piecewise quadratic along the search direction (the
@@ -3444,10 +3502,15 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
    termination test as solve_newton; the direction is the M^-1-preconditioned gradient, solved with
    the smooth factor of M that forward() left in L[] / Dk / Di (DinvM: this lane's 1/D), with
    Polak-Ribiere beta = max(0, g . (Mg - Mg_prev) / max(MINVAL, g_prev . Mg_prev)). No Hessian is
-   built or factored. Returns qacc (dof lane). */
-template <int XG, bool XA = true>
+   built or factored. Returns qacc (dof lane).
+   qacc_only (team-uniform): the caller reads nothing but the returned qacc and iters, as every
+   substep but a control step's last does when the damping is explicit (no sensors read the rows'
+   forces, no implicit_damping reads ftot). The iteration at the cap then ends with its step.
+   FOLD, GN: the masks folded into data (below; solve_prep's GN). forward() leaves them off for the
+   few instantiations that spilled more vector registers with them. */
+template <int XG, bool XA = true, bool FOLD = true, bool GN = true>
 __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float fs, float w, int& iters, bool live,
-                                          float DinvM, float& ftot) {
+                                          float DinvM, float& ftot, bool qacc_only) {
   CP cfg = c.cfg;
   MP m = c.m;
   EnvL* L = c.L;
@@ -3458,7 +3521,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   /* the lane's contact-row Jacobian: constant through the solve, kept in registers */
   float jr[CAP];
   ld_row(&L->u.J[c.l][0], jr);
-  float Ma = mul_m_dot(c, r, jr, x, V_TMP, jw, V_TMP2, js);
+  float Ma = mul_m_dot<FOLD>(c, r, jr, x, V_TMP, jw, V_TMP2, js);
   jw -= r.aref;
   js -= r.aref;
   float jwx = 0.f, jsx = 0.f;
@@ -3502,7 +3565,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   tsum_n<2>(cws);
   if (cws[0] > cws[1]) {
     x = qs;
-    Ma = mul_m(c, x, V_TMP);
+    Ma = mul_m<FOLD>(c, x, V_TMP);
     r.jar = js;
     r.x.jar = jsx;
     r.y.jar = jsy;
@@ -3518,9 +3581,16 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   r.jl = r.sl * x - r.al;
   const float scale = 1.0f / (m->meaninertia * (float)(NV > 1 ? NV : 1));
   float grad;
-  float cost = update_constraint<XG, XA, false>(c, r, jr, x, qs, fs, Ma, grad);
+  /* Lanes past the dofs (c.l >= NV) hold exact zeros in everything the loop sums, so the sums take
+     no c.l < NV mask: their M rows and their Q, U, g of solve_prep are zero (make_ctx; they sit on no
+     chain and are no root lane), which makes M y and M^-1 y zero there for any finite y; fs is zero
+     there (forward), hence qs = M^-1 fs; the warm start is zero there (load_state, reset_prepare,
+     integrate's w = qacc with forward's masked qacc), hence x, Ma and the Gauss term; the rows'
+     forces are added on dof lanes only (update_constraint_lane's qc), hence grad = Ma - fs - qc,
+     mg = M^-1 grad and search = -mg + beta search, and every step keeps x, Ma there. */
+  float cost = update_constraint<XG, XA, false, FOLD>(c, r, jr, x, qs, fs, Ma, grad);
   STAMP(S_UPD0);
-  float mg = solve_pre(c, grad);
+  float mg = solve_pre<GN>(c, grad);
   STAMP(S_SOLVE0);
   float search = -mg;
   int it = 0;
@@ -3528,19 +3598,29 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   while (live && it < itmax) {
     float Mv;
     STAMP(S_CHECK);
-    const float alpha = line_search<XG, XA>(c, r, jr, search, Ma, fs, grad, Mv);
+    const float alpha = line_search<XG, XA, FOLD>(c, r, jr, search, Ma, fs, grad, Mv);
     STAMP(S_LS);
     if (alpha == 0.f) break;
-    x += alpha * search;
+    /* x and r.jf (below) take the same product in two blocks since the exit between them, and the
+       compiler contracts a product into the add of its own block only. Both are written as the
+       compiler made them while they shared a block, which the recorded bits hold: x adds the rounded
+       product, r.jf is one fused multiply-add. */
+    x += rounded(alpha * search);
+    if (qacc_only && it + 1 == itmax) {
+      /* the cap: no further iteration, and the rows' state at the new point (M qacc, the row
+         values, forces, active set and gradient) has no reader */
+      it++;
+      break;
+    }
     Ma += alpha * Mv;
     r.jar += alpha * r.Jv;
     if constexpr (XG && XA) r.x.jar += alpha * r.x.Jv;
     if constexpr (YBANK<XG> && XA) r.y.jar += alpha * r.y.Jv;
     if constexpr (ZPAIR<XG> && XA) r.z.jar += alpha * r.z.Jv;
-    r.jf += alpha * search;
+    r.jf = __builtin_fmaf(alpha, search, r.jf);
     if (r.anyl) r.jl += alpha * (r.sl * search);
     const float oldcost = cost, gold = grad, mgold = mg;
-    const float cl = update_constraint_lane<XG, XA, false>(c, r, jr, x, qs, fs, Ma, grad);
+    const float cl = update_constraint_lane<XG, XA, false, FOLD>(c, r, jr, x, qs, fs, Ma, grad);
     STAMP(S_UPD);
     it++;
     /* MJX's order (solver.py: _update_gradient, then the Polak-Ribiere beta, then the termination
@@ -3549,10 +3629,15 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
        (the same DPP sequence per value: the bits of separate sums). An iteration at the cap skips the
        solve and the beta sums, which only feed the next iteration. */
     if (it < itmax) {
-      mg = solve_pre(c, grad);
+      mg = solve_pre<GN>(c, grad);
       STAMP(S_SOLVE);
       float red[4] = {cl, c.l < NV ? grad * grad : 0.f, c.l < NV ? grad * (mg - mgold) : 0.f,
                       c.l < NV ? gold * mgold : 0.f};
+      if constexpr (FOLD) { /* zeros past the dofs (above) */
+        red[1] = rounded(grad * grad);
+        red[2] = rounded(grad * (mg - mgold));
+        red[3] = rounded(gold * mgold);
+      }
       tsum_n<4>(red);
       cost = red[0];
       const float improvement = scale * (oldcost - cost);
@@ -3610,7 +3695,8 @@ __device__ __forceinline__ void feetech(const Ctx& c, LaneS& ls) {
 
 /* ------------------------------- full forward ------------------------------ */
 /* mj_forward (+ sensors if requested). Leaves qacc in ls.qacc, kinematics in B. */
-template <int SOLVER, int XG>
+/* FQ: the caller reads ls.fq after a pass without sensors (implicit_damping of the ED kernels) */
+template <int SOLVER, int XG, bool FQ = true>
 __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, BodyK& B, Rows& r, bool with_sensors,
                                         Sensors& sen, int& iters) {
   MP m = c.m;
@@ -3648,8 +3734,12 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   float fs = (c.l < NV) ? (-damp * ls.v - bias + act) : 0.f;
   STAMP(S_RNE);
   constexpr bool PRE = SOLVER == ZB_SOLVER_CG; /* CG's ~10 solves with M's factor per substep */
-  if constexpr (PRE) solve_prep(c);
-  float qs = PRE ? solve_pre(c, fs) : solve_ldl(c, fs, DinvM);
+  /* solve_cg's folded masks, bit-identical either way, are left off where the kernel spilled more
+     vector registers with them than without: the implicit-damping kernels of
+     XG 2 and 5 (27 against 25, 39 against 38), and solve_prep's -1 in XG 4 (51 against 41) */
+  constexpr bool FOLD = !(FQ && (XG == 2 || XG == 5)), GN = FOLD && XG != 4;
+  if constexpr (PRE) solve_prep<GN>(c);
+  float qs = PRE ? solve_pre<GN>(c, fs) : solve_ldl(c, fs, DinvM);
   STAMP(S_SOLVES);
   /* constraints */
   make_constraints<XG>(c, s, ls, B, cm, r);
@@ -3669,8 +3759,9 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
        r.x.any; branches on it inside the loops were if-converted into every evaluation) */
     auto solve = [&](auto xa) -> float {
       constexpr bool XA = decltype(xa)::value;
-      return SOLVER == ZB_SOLVER_CG ? solve_cg<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft)
-                                    : solve_newton<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
+      return SOLVER == ZB_SOLVER_CG
+                 ? solve_cg<XG, XA, FOLD, GN>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
+                 : solve_newton<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
     };
     const bool xa = XG != 0 && (r.x.any || (YBANK<XG> && r.y.any) || (ZPAIR<XG> && r.z.any)); /* wave-uniform */
     const float qn = xa ? solve(BoolC<true>{}) : solve(BoolC<false>{});
@@ -4445,7 +4536,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (!resetting && !ghost) feetech<XG>(c, ls);
       STAMP(S_FEETECH);
       int it_pass = 0;
-      forward<SOLVER, XG>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
+      forward<SOLVER, XG, ED != 0>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
       if (!ghost) iters += it_pass;
       if (!resetting && !ghost) {
         /* wave-uniform: both teams integrate, or both run the reset / ghost pass */

@@ -1,0 +1,187 @@
+"""Record the HIP engine's own output bits (needs the GPU): tests/golden/engine_bits_<case>.npz.
+
+    python tests/golden/make_engine_bits.py [--out DIR] [case ...]
+
+The other goldens pin the CPU oracle, and the engine is held to them within a tolerance. These
+pin the engine itself, bit for bit, so that a change meant to leave every rounding alone (fewer
+instructions, another schedule) can be told from one that does not. tests/test_gpu_engine_bits.py
+replays every case and compares with array_equal.
+
+A case runs 64 envs from reset with a fixed seed, and its first three envs again as an engine of
+n = 3 (an odd n: the last wave's second team is the ghost copy past n). It keeps the actions' noise
+(int8, in steps of 1/32: the float32 actions follow from it exactly), the
+per-step reward / done / success / solver_iters() rows, get_state() and get_rand() after the last
+step and every output of the last step. The collider and sole-pair cases start from states in
+which the rows in question exist (tests/collider_util.py), set with set_state() after the reset.
+
+Regenerating: when a change alters the engine's rounding on purpose, check it against the
+oracle-based tests first (tests/test_gpu_parity.py, tests/test_gpu_colliders.py), then run this
+script on the GPU at that commit and commit the new files together with the change; main() refuses
+to write a case that lost what makes it worth having (an episode end, a solve below the iteration
+cap, second-bank rows).
+"""
+
+import argparse
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.dirname(HERE)):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+N = 64
+N_ODD = 3  # the first three envs again, alone
+SIGMA = 0.2
+
+CASES = {
+    # (a) the headline kernel: CG, the default model
+    "cg": dict(steps=40, seed=21),
+    # (b) mj_Euler's implicit damping (the ED kernels)
+    "cg_eulerdamp": dict(steps=40, seed=22, eulerdamp=True),
+    # (c) pushes and per-env domain randomization
+    "cg_push_rand": dict(steps=40, seed=23, push=True, randomize=True),
+    # (d) Newton
+    "newton": dict(steps=8, seed=24, solver="newton"),
+    # (e) the second contact-row bank: floor colliders beyond the soles, from touching states
+    "cg_limbs": dict(steps=8, seed=25, model="zbot_like_limbs.xml", start="touching"),
+    "cg_many": dict(steps=8, seed=26, model="zbot_like_many.xml", start="touching"),
+    # (f) the sole pair, from states with the soles crossed
+    "cg_sole_pair": dict(steps=8, seed=27, model="sole_pair", start="crossing"),
+}
+
+
+def case_model(model=None):
+    from zbot_amd import compile_model  # noqa: PLC0415
+
+    if model is None:
+        return compile_model()
+    if model == "sole_pair":
+        import collider_util as U  # noqa: PLC0415
+
+        return compile_model(U.sole_pair_desc())
+    from zbot_amd.mjcf import load_mjcf  # noqa: PLC0415
+
+    return compile_model(load_mjcf(os.path.join(ROOT, "ksim-gym-zbot_amd", "assets", model)))
+
+
+def case_noise(steps, seed):
+    """[steps, N, 20] int8: N(0, 1) in steps of 1/32 (what the fixture keeps of its actions)."""
+    z = np.random.default_rng(seed).standard_normal((steps, N, 20))
+    return np.clip(np.rint(z * 32.0), -127, 127).astype(np.int8)
+
+
+def case_actions(cm, noise_q):
+    """[steps, N, 20] float32: the joint biases + SIGMA N(0, 1), exact in float32 from the int8 noise."""
+    bias = np.array([cm.cmodel.joint_bias[i] for i in range(20)], np.float32)
+    return bias + np.float32(SIGMA) * (noise_q.astype(np.float32) / np.float32(32.0))
+
+
+def start_qpos(cm, start, seed):
+    """[N, 27] qpos of a case that does not start from the reset state (None: it does)."""
+    if start is None:
+        return None
+    import collider_util as U  # noqa: PLC0415
+
+    if start == "touching":
+        return U.touching_states(cm, N, seed).astype(np.float32)
+    return U.crossing_states(cm, N, seed, air=False).astype(np.float32)
+
+
+def second_bank_envs(cm, qpos) -> int:
+    """Envs whose start state has a floor contact on a collider beyond the two soles."""
+    import collider_util as U  # noqa: PLC0415
+
+    return sum(any(len(cons) > 0 for cons in U.contacts(cm, q.astype(np.float64))[2:]) for q in qpos)
+
+
+def run_engine(cm, cfg, n, seed, actions, qpos):
+    """One engine of the first n envs through every step; the arrays a fixture keeps."""
+    import torch  # noqa: PLC0415
+    from zbot_amd import cstructs as cs  # noqa: PLC0415
+    from zbot_amd.engine import HipEngine  # noqa: PLC0415
+
+    eng = HipEngine(cm, cfg, n, seed=seed)
+    eng.reset()
+    if qpos is not None:
+        st = eng.get_state().cpu().numpy()
+        st[:, :27] = qpos[:n]
+        st[:, 32:58] = 0.0
+        st[:, cs.S_QACCW:cs.S_QACCW + 32] = 0.0
+        eng.set_state(torch.from_numpy(st))
+    rows = {"reward": [], "done": [], "success": [], "solver_iters": []}
+    out = None
+    for a in actions:
+        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[:n])).cuda())
+        torch.cuda.synchronize()
+        for k in ("reward", "done", "success"):
+            rows[k].append(out[k].cpu().numpy().copy())
+        rows["solver_iters"].append(eng.solver_iters().cpu().numpy())  # of this launch
+    d = {k: np.stack(v) for k, v in rows.items()}
+    d["final_state"] = eng.get_state().cpu().numpy()
+    d["final_rand"] = eng.get_rand().cpu().numpy()
+    for k, v in out.items():
+        d[f"last_{k}"] = v.cpu().numpy().copy()
+    return d
+
+
+def run_case(name, noise_q=None):
+    """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
+    kw = dict(CASES[name])
+    from zbot_amd import default_config  # noqa: PLC0415
+
+    cm = case_model(kw.get("model"))
+    cfg = default_config(solver=kw.get("solver", "cg"), eulerdamp=kw.get("eulerdamp", False),
+                         push=kw.get("push", False), randomize=kw.get("randomize", False))
+    if noise_q is None:
+        noise_q = case_noise(kw["steps"], kw["seed"])
+    actions = case_actions(cm, noise_q)
+    qpos = start_qpos(cm, kw.get("start"), kw["seed"])
+    data = {"noise_q": noise_q}
+    for tag, n in (("", N), ("odd_", N_ODD)):
+        for k, v in run_engine(cm, cfg, n, kw["seed"], actions, qpos).items():
+            data[tag + k] = v
+    return data, cm, cfg, qpos
+
+
+def check_case(name, data, cm, cfg, qpos) -> None:
+    """What makes the fixture worth having, on the run that is about to be recorded."""
+    kw = CASES[name]
+    assert np.isfinite(data["final_state"][:, :58]).all(), f"{name}: non-finite state"
+    if name == "cg":
+        # a control step: n_substeps solves of at most cfg.iterations iterations (a reset pass adds one)
+        cap = cfg.n_substeps * cfg.iterations
+        ends = int(data["done"].sum())
+        below = int((data["solver_iters"] < cap).sum())
+        print(f"  {name}: {ends} episode ends, {below} of {data['solver_iters'].size} env-steps below the cap total {cap}")
+        assert ends >= 1, f"{name}: no episode end in {kw['steps']} steps (the reset and ghost passes did not run)"
+        assert below >= 1, f"{name}: every solve ran to the iteration cap"
+    if kw.get("start") == "touching":
+        nb = second_bank_envs(cm, qpos)
+        print(f"  {name}: {nb} of {N} envs start with second-bank rows")
+        assert nb >= 1, f"{name}: no env has rows in the second bank"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
+    ap.add_argument("--out", default=HERE)
+    a = ap.parse_args()
+    os.makedirs(a.out, exist_ok=True)
+    for name in CASES:
+        if a.cases and name not in a.cases:
+            continue
+        data, cm, cfg, qpos = run_case(name)
+        check_case(name, data, cm, cfg, qpos)
+        path = os.path.join(a.out, f"engine_bits_{name}.npz")
+        np.savez_compressed(path, **data)
+        kb = os.path.getsize(path) / 1024
+        assert kb < 300, f"{path}: {kb:.0f} KB"
+        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
+
+
+if __name__ == "__main__":
+    main()
