@@ -82,6 +82,100 @@ int zb_moments_combine(const double* moments, int k, double* out, void* stream);
 int zb_adv_normalize(const float* gae, float* advantages, long long count, const double* moments,
                      double total, float eps, void* stream);
 
+/*
+ * ---- Learner: PPO loss seeds, global-norm clip and AdamW ----
+ *
+ * The three steps of an optimizer step around the networks' backward pass
+ * (include/zbot_policy.h "Training"):
+ *
+ *   zb_policy_actor_train / zb_policy_critic_train       log_prob, values
+ *   zb_ppo_loss                                          -> d_log_prob, d_value, sums
+ *   zb_policy_actor_backward / zb_policy_critic_backward -> one flat gradient per network
+ *   zb_grad_sqnorm (one per network)                     -> sqnorms[k]
+ *   zb_adamw_step  (one per network, the same sqnorms)   params, m, v in place
+ *   zb_policy_set_params
+ *
+ * Element arithmetic: include/zbot_learner_math.h, whose operation order is
+ * the definition. The loss is ksim's PPO loss [U] as zbot_amd.learner.ppo_loss
+ * states it (clipped surrogate on the log-probs summed over the 20 joints,
+ * clipped value loss, means over `total` rows; no entropy term); the update is
+ * optax.clip_by_global_norm -> optax.adamw [U] (train.py:1314-1324).
+ *
+ * All pointers are device pointers; every call is asynchronous on `stream`,
+ * allocates nothing and synchronizes nothing. Bad arguments return ZB_EARG and
+ * launch nothing.
+ *
+ * Reduction tree: every sum (the four loss sums over rows, the squared norm
+ * over elements) is the balanced pairwise tree over its leaves in index order,
+ * zero-padded to a power of two, combined in fp64; the root is then added to
+ * +0.0 (so a sum of negative zeros reads +0 whatever the padding). Adding
+ * zeros is exact, so the result depends neither on the launch shape nor, for
+ * power-of-two shards combined in rank order, on the world size. No
+ * floating-point atomics anywhere.
+ *
+ * The *_host functions take host pointers, run the same header and the same
+ * tree on the CPU, and are the bit reference of the kernels.
+ */
+#define ZB_LOSS_ROWS_PER_BLOCK 256     /* rows (leaves) per partial of zb_ppo_loss */
+#define ZB_SQNORM_ELEMS_PER_BLOCK 4096 /* elements (leaves) per partial of zb_grad_sqnorm */
+
+/* fp64 words of the `partials` scratch zb_ppo_loss needs for a [T, n] batch (0: bad size). */
+size_t zb_ppo_loss_partials_words(int T, int n);
+
+/*
+ * PPO loss seeds and sums over the T*n rows of a [T, n] minibatch.
+ *   log_prob, old_log_prob    [T, n, 20] fp32
+ *   advantages, values, old_values, value_targets  [T, n] fp32
+ *   total          rows the means run over: T*n here, T*n_global when ranks share a batch
+ *   d_log_prob     [T, n, 20] fp32: d loss / d log_prob (the same value for a row's 20 joints)
+ *   d_value        [T, n] fp32: d loss / d values
+ *   partials       [zb_ppo_loss_partials_words(T, n)] fp64 scratch
+ *   sums_out       [4] fp64 over this call's rows: sum S, sum Vt, sum [|ratio - 1| > clip_param],
+ *                  sum ((ratio - 1) - log ratio). loss = -sums[0] / total
+ *                  + value_loss_coef * 0.5 * sums[1] / total; sums[2] / total is the clip
+ *                  fraction, sums[3] / total an approximate KL.
+ * T >= 1, n >= 1, T*n <= 2^28, total > 0, clip_param >= 0, log_clip_value >= 0. Outputs alias no input.
+ */
+int zb_ppo_loss(const float* log_prob, const float* old_log_prob, const float* advantages, const float* values,
+                const float* old_values, const float* value_targets, int T, int n, double total, float clip_param,
+                float value_loss_coef, int use_clipped_value_loss, float log_clip_value, float* d_log_prob,
+                float* d_value, double* partials, double* sums_out, void* stream);
+int zb_ppo_loss_host(const float* log_prob, const float* old_log_prob, const float* advantages, const float* values,
+                     const float* old_values, const float* value_targets, int T, int n, double total,
+                     float clip_param, float value_loss_coef, int use_clipped_value_loss, float log_clip_value,
+                     float* d_log_prob, float* d_value, double* sums_out);
+
+/* fp64 words of the `partials` scratch zb_grad_sqnorm needs for `count` elements. */
+size_t zb_sqnorm_partials_words(size_t count);
+
+/*
+ * out[0] = sum_i grad[i]^2 (fp64; the square of an fp32 value is exact there), by the tree above.
+ * 1 <= count <= 2^32.
+ */
+int zb_grad_sqnorm(const float* grad, size_t count, double* partials, double* out, void* stream);
+int zb_grad_sqnorm_host(const float* grad, size_t count, double* out);
+
+/*
+ * One AdamW step behind the global-norm clip, in place on param, m, v [count] (fp32):
+ *   N = sqrt(sqnorms[0] + ... + sqnorms[k-1])  (fp64, index order): the joint norm of k gradients,
+ *       e.g. the actor's and the critic's, each from zb_grad_sqnorm;
+ *   scale = (float)(max_grad_norm / N) if max_grad_norm > 0 and N > max_grad_norm, else exactly 1;
+ *   zbl_adamw (zbot_learner_math.h) on elements 0 .. count - frozen_tail - 1.
+ * The last `frozen_tail` elements of param, m and v are left untouched (the actor's 20 mean
+ * offsets, constants of the model). `step` >= 1 is the number of this step, counted by the caller;
+ * the bias corrections 1 - beta^step are formed from it on the host in fp64. beta1 and beta2 are
+ * doubles because 1 - beta is formed from them too, in fp64, and rounded once (zbot_learner_math.h). It is passed by value:
+ * a captured graph replays the step number it was captured with, so capture would freeze the bias
+ * correction; launch this call outside a graph, or re-capture per step.
+ * 1 <= k <= 64, 0 <= beta < 1, lr, eps, weight_decay >= 0.
+ */
+int zb_adamw_step(float* param, const float* grad, float* m, float* v, size_t count, size_t frozen_tail,
+                  const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2, float eps,
+                  float weight_decay, int step, void* stream);
+int zb_adamw_step_host(float* param, const float* grad, float* m, float* v, size_t count, size_t frozen_tail,
+                       const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2,
+                       float eps, float weight_decay, int step);
+
 #ifdef __cplusplus
 }
 #endif

@@ -431,6 +431,81 @@ int zb_adv_normalize(const float* gae, float* advantages, long long count, const
   return ZB_OK;
 }
 
+/* ---- learner: loss seeds, gradient norm, AdamW (include/zbot_ppo.h "Learner") ---- */
+
+size_t zb_ppo_loss_partials_words(int T, int n) {
+  if (T < 1 || n < 1) return 0;
+  const size_t rows = (size_t)T * (size_t)n;
+  return 4 * ((rows + ZB_LOSS_ROWS_PER_BLOCK - 1) / ZB_LOSS_ROWS_PER_BLOCK);
+}
+
+int zb_ppo_loss(const float* log_prob, const float* old_log_prob, const float* advantages, const float* values,
+                const float* old_values, const float* value_targets, int T, int n, double total, float clip_param,
+                float value_loss_coef, int use_clipped_value_loss, float log_clip_value, float* d_log_prob,
+                float* d_value, double* partials, double* sums_out, void* stream) {
+  const void* ptrs[] = {log_prob, old_log_prob, advantages, values, old_values, value_targets, d_log_prob, d_value,
+                        partials, sums_out};
+  if (int rc = zb::check_loss_args("zb_ppo_loss", ptrs, 10, T, n, total, clip_param, log_clip_value)) return rc;
+  zb::LossArgs a;
+  a.log_prob = log_prob;
+  a.old_log_prob = old_log_prob;
+  a.advantages = advantages;
+  a.values = values;
+  a.old_values = old_values;
+  a.value_targets = value_targets;
+  a.rows = (size_t)T * (size_t)n;
+  a.inv = zb::inv_total(total);
+  a.clip_param = clip_param;
+  a.value_loss_coef = value_loss_coef;
+  a.log_clip_value = log_clip_value;
+  a.use_clipped_value_loss = use_clipped_value_loss ? 1 : 0;
+  a.d_log_prob = d_log_prob;
+  a.d_value = d_value;
+  a.partials = partials;
+  a.vec = 0;
+  hipError_t e = zb::launch_ppo_loss(a, sums_out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_ppo_loss launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+size_t zb_sqnorm_partials_words(size_t count) {
+  return (count + ZB_SQNORM_ELEMS_PER_BLOCK - 1) / ZB_SQNORM_ELEMS_PER_BLOCK;
+}
+
+int zb_grad_sqnorm(const float* grad, size_t count, double* partials, double* out, void* stream) {
+  if (int rc = zb::check_sqnorm_args("zb_grad_sqnorm", grad, count, out)) return rc;
+  if (!partials) return fail(ZB_EARG, "zb_grad_sqnorm: null partials");
+  hipError_t e = zb::launch_sqnorm(grad, count, partials, out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_grad_sqnorm launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+int zb_adamw_step(float* param, const float* grad, float* m, float* v, size_t count, size_t frozen_tail,
+                  const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2, float eps,
+                  float weight_decay, int step, void* stream) {
+  if (int rc = zb::check_adamw_args("zb_adamw_step", param, grad, m, v, count, frozen_tail, sqnorms, k, max_grad_norm,
+                                    lr, beta1, beta2, eps, weight_decay, step))
+    return rc;
+  zb::AdamArgs a;
+  a.param = param;
+  a.grad = grad;
+  a.m = m;
+  a.v = v;
+  a.count = count;
+  a.frozen_tail = frozen_tail;
+  a.sqnorms = sqnorms;
+  a.k = k;
+  a.max_grad_norm = max_grad_norm;
+  a.lr = lr;
+  a.c = zb::adam_coefficients(beta1, beta2, step);
+  a.eps = eps;
+  a.wd = weight_decay;
+  a.vec = 0;
+  hipError_t e = zb::launch_adamw(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_adamw_step launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
 /* ---- GRU policy / value networks (include/zbot_policy.h) ---- */
 
 struct ZbPolicy {

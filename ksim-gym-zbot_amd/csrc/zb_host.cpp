@@ -1,6 +1,8 @@
 /*
  * zb_host.cpp — the host-only half of the C ABI (include/zbot.h): the error string, the
- * train.py default configuration, model / config validation and the per-lane team topology.
+ * train.py default configuration, model / config validation and the per-lane team topology;
+ * and the learner's host twins (include/zbot_ppo.h "Learner": zb_ppo_loss_host,
+ * zb_grad_sqnorm_host, zb_adamw_step_host), the CPU bit reference of csrc/zb_learner.hip.
  * Plain C++ (no HIP): the product library links it, and csrc/sanitize.mk builds it with the host
  * sanitizers for tests/test_sanitizers.py.
  */
@@ -13,6 +15,10 @@
 #include <string.h>
 
 #include <string>
+#include <vector>
+
+#include "zbot_learner_math.h"
+#include "zbot_ppo.h"
 
 namespace zb {
 
@@ -320,11 +326,121 @@ void build_topology(const ZbModel* m, int32_t t[zb::TP_NF][zb::TOPO_LANES]) {
   }
 }
 
+/* ---- learner (include/zbot_ppo.h "Learner"): argument checks and the host twins' tree ---- */
+
+int check_loss_args(const char* what, const void* const* ptrs, int nptrs, int T, int n, double total,
+                    float clip_param, float log_clip_value) {
+  for (int i = 0; i < nptrs; i++)
+    if (!ptrs[i]) return fail(ZB_EARG, "%s: null pointer (argument %d of its arrays)", what, i + 1);
+  if (T < 1 || n < 1) return fail(ZB_EARG, "%s: bad size (T=%d n=%d)", what, T, n);
+  if ((unsigned long long)T * (unsigned long long)n > (1ull << 28))
+    return fail(ZB_EARG, "%s: T n = %llu rows exceed 2^28", what, (unsigned long long)T * n);
+  if (!(total > 0.0)) return fail(ZB_EARG, "%s: total must be > 0", what);
+  if (!(clip_param >= 0.f) || !(log_clip_value >= 0.f))
+    return fail(ZB_EARG, "%s: clip_param / log_clip_value must be >= 0", what);
+  return ZB_OK;
+}
+
+int check_sqnorm_args(const char* what, const void* grad, size_t count, const void* out) {
+  if (!grad || !out) return fail(ZB_EARG, "%s: null pointer", what);
+  if (count < 1 || (unsigned long long)count > (1ull << 32))
+    return fail(ZB_EARG, "%s: count = %zu (1 to 2^32)", what, count);
+  return ZB_OK;
+}
+
+int check_adamw_args(const char* what, const void* param, const void* grad, const void* m, const void* v,
+                     size_t count, size_t frozen_tail, const void* sqnorms, int k, float max_grad_norm, float lr,
+                     double beta1, double beta2, float eps, float weight_decay, int step) {
+  if (!param || !grad || !m || !v || !sqnorms) return fail(ZB_EARG, "%s: null pointer", what);
+  if (count < 1 || (unsigned long long)count > (1ull << 32))
+    return fail(ZB_EARG, "%s: count = %zu (1 to 2^32)", what, count);
+  if (frozen_tail > count) return fail(ZB_EARG, "%s: frozen_tail %zu > count %zu", what, frozen_tail, count);
+  if (k < 1 || k > 64) return fail(ZB_EARG, "%s: k = %d norms (1 to 64)", what, k);
+  if (step < 1) return fail(ZB_EARG, "%s: step = %d (the first step is 1)", what, step);
+  if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
+    return fail(ZB_EARG, "%s: beta1 / beta2 must lie in [0, 1)", what);
+  if (!(lr >= 0.f) || !(eps >= 0.f) || !(weight_decay >= 0.f) || max_grad_norm != max_grad_norm)
+    return fail(ZB_EARG, "%s: lr / eps / weight_decay must be >= 0, max_grad_norm a number", what);
+  return ZB_OK;
+}
+
+float inv_total(double total) { return (float)(1.0 / total); }
+
+AdamCoef adam_coefficients(double beta1, double beta2, int step) {
+  AdamCoef c;
+  c.beta1 = (float)beta1;
+  c.omb1 = (float)(1.0 - beta1);
+  c.beta2 = (float)beta2;
+  c.omb2 = (float)(1.0 - beta2);
+  c.bc1 = (float)(1.0 - std::pow(beta1, (double)step));
+  c.bc2 = (float)(1.0 - std::pow(beta2, (double)step));
+  return c;
+}
+
+/* The balanced pairwise tree over leaves [lo, lo + len), len a power of two, of which the first
+   `count` exist (the rest are +0.0): leaf(i) for a single leaf, left + right otherwise. */
+template <typename Leaf>
+static double tree_sum(const Leaf& leaf, size_t lo, size_t len, size_t count) {
+  if (lo >= count) return 0.0;
+  if (len == 1) return leaf(lo);
+  const double a = tree_sum(leaf, lo, len / 2, count);
+  const double b = tree_sum(leaf, lo + len / 2, len / 2, count);
+  return a + b;
+}
+template <typename Leaf>
+static double tree_root(const Leaf& leaf, size_t count) {
+  size_t len = 1;
+  while (len < count) len <<= 1;
+  return tree_sum(leaf, 0, len, count) + 0.0;
+}
+
 }  // namespace zb
 
 using zb::fail;
 
 extern "C" {
+
+int zb_ppo_loss_host(const float* log_prob, const float* old_log_prob, const float* advantages, const float* values,
+                     const float* old_values, const float* value_targets, int T, int n, double total,
+                     float clip_param, float value_loss_coef, int use_clipped_value_loss, float log_clip_value,
+                     float* d_log_prob, float* d_value, double* sums_out) {
+  const void* ptrs[] = {log_prob, old_log_prob, advantages, values, old_values, value_targets, d_log_prob, d_value, sums_out};
+  if (int rc = zb::check_loss_args("zb_ppo_loss_host", ptrs, 9, T, n, total, clip_param, log_clip_value)) return rc;
+  const size_t rows = (size_t)T * (size_t)n;
+  const float inv = zb::inv_total(total);
+  std::vector<ZblLossRow> r(rows);
+  for (size_t i = 0; i < rows; i++) {
+    const float s = zbl_joint_sum(log_prob + i * ZBL_JOINTS), s0 = zbl_joint_sum(old_log_prob + i * ZBL_JOINTS);
+    zbl_loss_row(s, s0, advantages[i], values[i], old_values[i], value_targets[i], clip_param, log_clip_value,
+                 value_loss_coef, inv, use_clipped_value_loss, &r[i]);
+    for (int j = 0; j < ZBL_JOINTS; j++) d_log_prob[i * ZBL_JOINTS + j] = r[i].d_log_prob;
+    d_value[i] = r[i].d_value;
+  }
+  sums_out[0] = zb::tree_root([&](size_t i) { return (double)r[i].surrogate; }, rows);
+  sums_out[1] = zb::tree_root([&](size_t i) { return (double)r[i].value_term; }, rows);
+  sums_out[2] = zb::tree_root([&](size_t i) { return (double)r[i].clipped; }, rows);
+  sums_out[3] = zb::tree_root([&](size_t i) { return (double)r[i].kl; }, rows);
+  return ZB_OK;
+}
+
+int zb_grad_sqnorm_host(const float* grad, size_t count, double* out) {
+  if (int rc = zb::check_sqnorm_args("zb_grad_sqnorm_host", grad, count, out)) return rc;
+  out[0] = zb::tree_root([&](size_t i) { const double g = (double)grad[i]; return g * g; }, count);
+  return ZB_OK;
+}
+
+int zb_adamw_step_host(float* param, const float* grad, float* m, float* v, size_t count, size_t frozen_tail,
+                       const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2,
+                       float eps, float weight_decay, int step) {
+  if (int rc = zb::check_adamw_args("zb_adamw_step_host", param, grad, m, v, count, frozen_tail, sqnorms, k,
+                                    max_grad_norm, lr, beta1, beta2, eps, weight_decay, step))
+    return rc;
+  const zb::AdamCoef c = zb::adam_coefficients(beta1, beta2, step);
+  const float scale = zbl_clip_scale(sqnorms, k, max_grad_norm);
+  for (size_t i = 0; i < count - frozen_tail; i++)
+    zbl_adamw(&param[i], &m[i], &v[i], grad[i], scale, lr, c.beta1, c.omb1, c.beta2, c.omb2, c.bc1, c.bc2, eps, weight_decay);
+  return ZB_OK;
+}
 
 const char* zb_last_error(void) { return zb::g_err.c_str(); }
 

@@ -7,6 +7,7 @@
 #ifndef ZB_HOST_H
 #define ZB_HOST_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "zbot.h"
@@ -36,6 +37,20 @@ int needs_xg(const ZbModel* m); /* 0 two-sole, 1 general colliders, 2 with cylin
 int bank_cap(const ZbModel* m);
 /* requires check_model(m) == ZB_OK */
 void build_topology(const ZbModel* m, int32_t t[TP_NF][TOPO_LANES]);
+
+/* argument checks of the learner entry points (include/zbot_ppo.h "Learner"), shared by the
+   device entry points (zb_capi.cpp) and their host twins: ZB_OK or ZB_EARG */
+int check_loss_args(const char* what, const void* const* ptrs, int nptrs, int T, int n, double total,
+                    float clip_param, float log_clip_value);
+int check_sqnorm_args(const char* what, const void* grad, size_t count, const void* out);
+int check_adamw_args(const char* what, const void* param, const void* grad, const void* m, const void* v,
+                     size_t count, size_t frozen_tail, const void* sqnorms, int k, float max_grad_norm, float lr,
+                     double beta1, double beta2, float eps, float weight_decay, int step);
+/* the scalars both sides derive on the host, here only (zb_capi.cpp is built with relaxed flags):
+   (float)(1 / total); AdamW's (float)beta, (float)(1 - beta), (float)(1 - beta^step), in fp64 */
+float inv_total(double total);
+struct AdamCoef { float beta1, omb1, beta2, omb2, bc1, bc2; };
+AdamCoef adam_coefficients(double beta1, double beta2, int step);
 
 }  // namespace zb
 

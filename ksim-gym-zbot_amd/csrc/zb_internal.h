@@ -182,6 +182,39 @@ hipError_t launch_policy_pack(int kind, const float* params, float* wpack, float
 hipError_t launch_normalize(const float* gae, float* adv, long long count, const double* mom, double total,
                             float eps, hipStream_t s);
 
+/* the learner's loss / norm / AdamW kernels (zb_learner.hip, include/zbot_ppo.h "Learner") */
+struct LossArgs {
+  const float* log_prob;       /* [rows][20] */
+  const float* old_log_prob;   /* [rows][20] */
+  const float* advantages;     /* [rows] */
+  const float* values;
+  const float* old_values;
+  const float* value_targets;
+  size_t rows;                 /* T n */
+  float inv;                   /* (float)(1 / total) */
+  float clip_param, value_loss_coef, log_clip_value;
+  int use_clipped_value_loss;
+  float* d_log_prob;           /* [rows][20] */
+  float* d_value;              /* [rows] */
+  double* partials;            /* [ceil(rows / ZB_LOSS_ROWS_PER_BLOCK)][4] */
+  int vec;                     /* set by the launcher: the [rows][20] arrays are 16-byte aligned */
+};
+struct AdamArgs {
+  float* param;
+  const float* grad;
+  float* m;
+  float* v;
+  size_t count, frozen_tail;
+  const double* sqnorms;       /* [k] */
+  int k;
+  float max_grad_norm, lr, eps, wd;
+  AdamCoef c;                  /* zb_host.h adam_coefficients */
+  int vec;                     /* set by the launcher: all four arrays are 16-byte aligned */
+};
+hipError_t launch_ppo_loss(LossArgs a, double* sums_out, hipStream_t s);
+hipError_t launch_sqnorm(const float* grad, size_t count, double* partials, double* out, hipStream_t s);
+hipError_t launch_adamw(AdamArgs a, hipStream_t s);
+
 }  // namespace zb
 
 #endif

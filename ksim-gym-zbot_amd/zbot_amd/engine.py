@@ -82,6 +82,23 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.zb_adv_normalize.argtypes = [vp, vp, C.c_longlong, vp, C.c_double, C.c_float, vp]
     for f in ("zb_gae", "zb_moments_combine", "zb_adv_normalize"):
         getattr(L, f).restype = C.c_int
+    # learner: loss seeds, gradient norm, AdamW (include/zbot_ppo.h "Learner") and their host twins
+    fl = C.c_float
+    L.zb_ppo_loss_partials_words.argtypes = [C.c_int, C.c_int]
+    L.zb_ppo_loss_partials_words.restype = C.c_size_t
+    L.zb_sqnorm_partials_words.argtypes = [C.c_size_t]
+    L.zb_sqnorm_partials_words.restype = C.c_size_t
+    loss_args = [vp] * 6 + [C.c_int, C.c_int, C.c_double, fl, fl, C.c_int, fl]
+    L.zb_ppo_loss.argtypes = loss_args + [vp, vp, vp, vp, vp]
+    L.zb_ppo_loss_host.argtypes = loss_args + [vp, vp, vp]
+    L.zb_grad_sqnorm.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    L.zb_grad_sqnorm_host.argtypes = [vp, C.c_size_t, vp]
+    adam_args = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, fl, fl, C.c_double, C.c_double, fl, fl, C.c_int]
+    L.zb_adamw_step.argtypes = adam_args + [vp]
+    L.zb_adamw_step_host.argtypes = adam_args
+    for f in ("zb_ppo_loss", "zb_ppo_loss_host", "zb_grad_sqnorm", "zb_grad_sqnorm_host", "zb_adamw_step",
+              "zb_adamw_step_host"):
+        getattr(L, f).restype = C.c_int
     # GRU actor / critic (include/zbot_policy.h)
     L.zb_policy_param_count.argtypes = [C.c_int]
     L.zb_policy_param_count.restype = C.c_size_t

@@ -7,7 +7,9 @@ optimizer is ZbotWalkingTask.get_optimizer (train.py:1314-1324).
 
 The hot path — the activation-saving forward and the backward pass through 5 GRU layers x T
 steps — runs in libzbot_hip.so (include/zbot_policy.h "Training"); there is no PyTorch or CPU
-fallback for it. The loss and the optimizer are ordinary torch:
+fallback for it. In PpoLearner the loss and the optimizer are ordinary torch; HipPpoLearner runs
+the same update with those steps in the library too (include/zbot_ppo.h "Learner"), and the torch
+path stays as the second implementation it is compared with:
 
     actor, critic = GruPolicy(ACTOR, ...), GruPolicy(CRITIC, ...)
     ta, tc = TrainablePolicy(actor), TrainablePolicy(critic)
@@ -198,3 +200,139 @@ class PpoLearner:
         self.actor.sync()
         self.critic.sync()
         return losses
+
+
+class HipPpoLearner:
+    """PpoLearner with every step in libzbot_hip.so (include/zbot_ppo.h "Learner"): per minibatch
+    the training forwards, zb_ppo_loss, the backward passes, two zb_grad_sqnorm, two zb_adamw_step
+    behind optax's global-norm clip over the joint norm, and zb_policy_set_params. No autograd
+    graph and no host synchronisation inside update(); every sum runs over a fixed fp64 tree, so an
+    update is bit-reproducible. Same constructor arguments and update() signature as PpoLearner;
+    `actor` / `critic` are GruPolicy handles or TrainablePolicy wrappers (whose `param` is brought
+    up to date at the end of update()).
+
+    The learner owns, per network, the flat parameters and AdamW's m and v (float32 device tensors,
+    natural layout) and the step count; state_dict() / load_state_dict() carry them."""
+
+    def __init__(self, learning_rate: float = DEFAULT_LEARNING_RATE, max_grad_norm: float = DEFAULT_MAX_GRAD_NORM,
+                 weight_decay: float = DEFAULT_WEIGHT_DECAY):
+        import torch  # noqa: PLC0415
+
+        self.torch = torch
+        self.learning_rate, self.max_grad_norm, self.weight_decay = learning_rate, max_grad_norm, weight_decay
+        self.actor = self.critic = None  # the GruPolicy handles the state below belongs to
+        self.step = 0                    # optimizer steps taken
+        self.state = None                # {"actor": {"params", "m", "v"}, "critic": {...}}
+        self._loaded = False             # state came from load_state_dict: the next update pushes it to its handles
+        self._buf = {}
+
+    @staticmethod
+    def _handle(p) -> GruPolicy:
+        return p.policy if isinstance(p, TrainablePolicy) else p
+
+    def _bind(self, actor: GruPolicy, critic: GruPolicy) -> None:
+        torch = self.torch
+        if actor.kind != ACTOR or critic.kind == ACTOR:
+            raise ZbError("HipPpoLearner.update(actor, critic): an actor and a critic handle, in this order")
+        if self._loaded:
+            for net, h in (("actor", actor), ("critic", critic)):
+                st = self.state[net]
+                for k in ("params", "m", "v"):
+                    st[k] = st[k].to(device=h.device, dtype=torch.float32).contiguous()
+                    if st[k].numel() != h.params_tensor().numel():
+                        raise ZbError(f"loaded {net} {k}: {st[k].numel()} elements for this handle")
+                h.set_params(st["params"])
+            self._loaded = False
+        elif self.state is None or actor is not self.actor or critic is not self.critic:
+            self.state, self.step = {}, 0
+            for net, h in (("actor", actor), ("critic", critic)):
+                p = h.params_tensor()
+                self.state[net] = dict(params=p, m=torch.zeros_like(p), v=torch.zeros_like(p))
+        self.actor, self.critic = actor, critic
+        dev = actor.device
+        if self._buf.get("dev") != dev:
+            from . import ppo  # noqa: PLC0415
+
+            L = ppo.load_library()
+            self._buf = dict(dev=dev, sq=torch.zeros(2, dtype=torch.float64, device=dev))
+            for net in ("actor", "critic"):
+                cnt = self.state[net]["params"].numel()
+                self._buf[net] = dict(grad=torch.empty(cnt, dtype=torch.float32, device=dev),
+                                      part=torch.empty(max(int(L.zb_sqnorm_partials_words(cnt)), 1),
+                                                       dtype=torch.float64, device=dev))
+
+    def update(self, rollout: dict, ppo_inputs, actor, critic, actor_carry0, critic_carry0, reset=None,
+               num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, **loss_kw) -> list:
+        """One PPO update, as PpoLearner.update (same arguments, same minibatches in the same order).
+        Returns one float64 device tensor [6] per optimizer step: zb_ppo_loss's four sums (sum S,
+        sum Vt, sum clipped, sum kl), then the row count and value_loss_coef the step used; loss(sums)
+        forms the scalar loss from it. Nothing is synchronized."""
+        from . import ppo  # noqa: PLC0415
+
+        torch = self.torch
+        wrappers = [p for p in (actor, critic) if isinstance(p, TrainablePolicy)]
+        self._bind(self._handle(actor), self._handle(critic))
+        act, cri, sa, sc, ba, bc, sq = (self.actor, self.critic, self.state["actor"], self.state["critic"],
+                                        self._buf["actor"], self._buf["critic"], self._buf["sq"])
+        T = rollout["actions"].shape[0]
+        n = rollout["actions"].shape[1]
+        if reset is None:
+            reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
+            reset[1:] = rollout["done"][:T - 1]
+        coef = float(loss_kw.get("value_loss_coef", DEFAULT_VALUE_LOSS_COEF))
+        out = []
+        for _ in range(num_passes):
+            for lo in range(0, n, batch_size):
+                hi = min(n, lo + batch_size)
+
+                def cut(x):
+                    return x[:T, lo:hi].contiguous()
+
+                obs_a, acts, obs_c, rs = cut(rollout["obs_actor"]), cut(rollout["actions"]), cut(rollout["obs_critic"]), cut(reset)
+                ca, cc = actor_carry0[lo:hi].contiguous(), critic_carry0[lo:hi].contiguous()
+                lp, scr_a = act.actor_train(obs_a, acts, ca, rs)
+                v, scr_c = cri.critic_train(obs_c, cc, rs)
+                sums = torch.empty(6, dtype=torch.float64, device=lp.device)
+                sums[4], sums[5] = float(T * (hi - lo)), coef
+                d_lp, d_v, _ = ppo.ppo_loss_grad(lp, cut(rollout["log_prob"]), cut(ppo_inputs.advantages_t), v,
+                                                 cut(rollout["value"]), cut(ppo_inputs.value_targets_t), sums=sums,
+                                                 **loss_kw)
+                # the critic first: its saved activations were written last, so more of them are still in
+                # the cache (autograd runs PpoLearner's backward passes in this order too)
+                cri.critic_backward(obs_c, cc, rs, d_v, scr_c, grad=bc["grad"])
+                act.actor_backward(obs_a, acts, ca, rs, d_lp, scr_a, grad=ba["grad"])
+                ppo.grad_sqnorm(ba["grad"], out=sq[0:1], partials=ba["part"])
+                ppo.grad_sqnorm(bc["grad"], out=sq[1:2], partials=bc["part"])
+                self.step += 1
+                for st, b, tail in ((sa, ba, JOINTS), (sc, bc, 0)):
+                    ppo.adamw_step(st["params"], b["grad"], st["m"], st["v"], sq, self.step, self.learning_rate,
+                                   max_grad_norm=self.max_grad_norm, weight_decay=self.weight_decay, frozen_tail=tail)
+                act.set_params(sa["params"])
+                cri.set_params(sc["params"])
+                out.append(sums)
+        for w in wrappers:  # a TrainablePolicy's own copy follows its handle
+            with torch.no_grad():
+                w.param.copy_(self.state["actor" if w.policy.kind == ACTOR else "critic"]["params"])
+            w._pushed = w.param._version
+        return out
+
+    @staticmethod
+    def loss(sums):
+        """The scalar PPO loss of one step from update()'s sums (a float64 device scalar; no sync):
+        -sum S / total + value_loss_coef * 0.5 * sum Vt / total, i.e. learner.ppo_loss."""
+        return -sums[0] / sums[4] + sums[5] * 0.5 * sums[1] / sums[4]
+
+    def state_dict(self) -> dict:
+        """{"step", "actor": {"params", "m", "v"}, "critic": {...}} (copies)."""
+        if self.state is None:
+            raise ZbError("HipPpoLearner.state_dict(): no state yet (no update() and no load_state_dict())")
+        return dict(step=self.step, **{net: {k: t.clone() for k, t in self.state[net].items()}
+                                       for net in ("actor", "critic")})
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore state_dict()'s result. The next update() pushes the restored parameters to the
+        handles it is given and continues the step count."""
+        self.state = {net: {k: sd[net][k].clone() for k in ("params", "m", "v")} for net in ("actor", "critic")}
+        self.step = int(sd["step"])
+        self.actor = self.critic = None
+        self._loaded = True

@@ -174,3 +174,174 @@ def compute_ppo_inputs(values_t, rewards_t, dones_t, successes_t=None, decay_gam
         total = global_count(g.numel(), group)
         adv = normalize(g, gm, total)
     return PPOInputs(advantages_t=adv, value_targets_t=vt, gae_t=g, returns_t=vt)
+
+
+# ---- the learner's three steps around the backward pass (include/zbot_ppo.h "Learner") ----
+# zbot_amd.learner's defaults (ksim PPOConfig [U]; optax.adamw [U]), repeated here because learner imports this module
+_CLIP_PARAM, _VALUE_LOSS_COEF, _USE_CLIPPED_VALUE_LOSS, _LOG_CLIP_VALUE = 0.2, 0.5, True, 10.0
+ADAM_BETA1, ADAM_BETA2, ADAM_EPS = 0.9, 0.999, 1e-8  # optax.adamw's defaults [U], torch.optim.AdamW's too
+JOINTS = 20
+
+
+def _f32_dev(t, dev, torch, name):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+        raise ZbError(f"{name} must be a contiguous float32 tensor on {dev}")
+    return t
+
+
+def _f64_dev(t, dev, torch, name, numel):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != dev or not t.is_contiguous()
+            or t.numel() < numel):
+        raise ZbError(f"{name} must be a contiguous float64 tensor of at least {numel} elements on {dev}")
+    return t
+
+
+def ppo_loss_grad(log_prob, old_log_prob, advantages, values, old_values, value_targets, total: float | None = None,
+                  clip_param: float = _CLIP_PARAM, value_loss_coef: float = _VALUE_LOSS_COEF,
+                  use_clipped_value_loss: bool = _USE_CLIPPED_VALUE_LOSS, log_clip_value: float = _LOG_CLIP_VALUE,
+                  d_log_prob=None, d_value=None, sums=None, partials=None):
+    """zb_ppo_loss: the seeds of learner.ppo_loss's gradient and its sums, on the GPU, asynchronously.
+
+    log_prob / old_log_prob [T, n, 20]; advantages, values, old_values, value_targets [T, n] (float32,
+    contiguous, one device). total: rows the means run over (default T n).
+    -> (d_log_prob [T, n, 20], d_value [T, n], sums [4] float64: sum S, sum Vt, sum clipped, sum kl);
+    loss = -sums[0] / total + value_loss_coef * 0.5 * sums[1] / total. The optional outputs and the
+    `partials` scratch are reused when given (sums may be longer than 4: the first 4 are written)."""
+    import torch  # noqa: PLC0415
+
+    L = load_library()
+    dev = log_prob.device
+    if dev.type != "cuda":
+        raise ZbError("ppo.ppo_loss_grad runs on the GPU (libzbot_hip.so); ppo_loss_grad_host is the CPU twin")
+    if log_prob.dim() != 3 or log_prob.shape[2] != JOINTS:
+        raise ZbError(f"log_prob must be [T, n, {JOINTS}], got {list(log_prob.shape)}")
+    T, n, _ = log_prob.shape
+    _f32_dev(log_prob, dev, torch, "log_prob")
+    if tuple(_f32_dev(old_log_prob, dev, torch, "old_log_prob").shape) != (T, n, JOINTS):
+        raise ZbError(f"old_log_prob must be [{T}, {n}, {JOINTS}]")
+    for name, t in (("advantages", advantages), ("values", values), ("old_values", old_values),
+                    ("value_targets", value_targets)):
+        if tuple(_f32_dev(t, dev, torch, name).shape) != (T, n):
+            raise ZbError(f"{name} must be [{T}, {n}], got {tuple(t.shape)}")
+    if d_log_prob is None:
+        d_log_prob = torch.empty(T, n, JOINTS, dtype=torch.float32, device=dev)
+    elif _f32_dev(d_log_prob, dev, torch, "d_log_prob").numel() != T * n * JOINTS:
+        raise ZbError(f"d_log_prob must hold {T * n * JOINTS} elements")
+    if d_value is None:
+        d_value = torch.empty(T, n, dtype=torch.float32, device=dev)
+    elif _f32_dev(d_value, dev, torch, "d_value").numel() != T * n:
+        raise ZbError(f"d_value must hold {T * n} elements")
+    words = int(L.zb_ppo_loss_partials_words(T, n))
+    partials = (torch.empty(max(words, 1), dtype=torch.float64, device=dev) if partials is None
+                else _f64_dev(partials, dev, torch, "partials", words))
+    sums = torch.empty(4, dtype=torch.float64, device=dev) if sums is None else _f64_dev(sums, dev, torch, "sums", 4)
+    _check(L.zb_ppo_loss(log_prob.data_ptr(), old_log_prob.data_ptr(), advantages.data_ptr(), values.data_ptr(),
+                         old_values.data_ptr(), value_targets.data_ptr(), T, n, float(T * n if total is None else total),
+                         C.c_float(clip_param), C.c_float(value_loss_coef), 1 if use_clipped_value_loss else 0,
+                         C.c_float(log_clip_value), d_log_prob.data_ptr(), d_value.data_ptr(), partials.data_ptr(),
+                         sums.data_ptr(), _stream(torch, dev)))
+    return d_log_prob, d_value, sums
+
+
+def grad_sqnorm(grad, out=None, partials=None):
+    """zb_grad_sqnorm: sum of squares of a float32 device tensor -> out [1] float64 (fixed fp64 tree)."""
+    import torch  # noqa: PLC0415
+
+    L = load_library()
+    dev = grad.device
+    if dev.type != "cuda":
+        raise ZbError("ppo.grad_sqnorm runs on the GPU (libzbot_hip.so); grad_sqnorm_host is the CPU twin")
+    _f32_dev(grad, dev, torch, "grad")
+    words = int(L.zb_sqnorm_partials_words(grad.numel()))
+    partials = (torch.empty(max(words, 1), dtype=torch.float64, device=dev) if partials is None
+                else _f64_dev(partials, dev, torch, "partials", words))
+    out = torch.empty(1, dtype=torch.float64, device=dev) if out is None else _f64_dev(out, dev, torch, "out", 1)
+    _check(L.zb_grad_sqnorm(grad.data_ptr(), grad.numel(), partials.data_ptr(), out.data_ptr(), _stream(torch, dev)))
+    return out
+
+
+def adamw_step(param, grad, m, v, sqnorms, step: int, lr: float, max_grad_norm: float = 0.0,
+               weight_decay: float = 0.0, frozen_tail: int = 0, beta1: float = ADAM_BETA1, beta2: float = ADAM_BETA2,
+               eps: float = ADAM_EPS) -> None:
+    """zb_adamw_step: one AdamW step of `param`, `m`, `v` (float32 device tensors, in place) behind the
+    global-norm clip over all of `sqnorms` (float64 device tensor of k squared norms; max_grad_norm
+    0: no clip). The last `frozen_tail` elements stay as they are. `step` counts from 1."""
+    import torch  # noqa: PLC0415
+
+    dev = param.device
+    if dev.type != "cuda":
+        raise ZbError("ppo.adamw_step runs on the GPU (libzbot_hip.so); adamw_step_host is the CPU twin")
+    for name, t in (("param", param), ("grad", grad), ("m", m), ("v", v)):
+        if _f32_dev(t, dev, torch, name).numel() != param.numel():
+            raise ZbError(f"{name} must hold {param.numel()} elements")
+    k = sqnorms.numel()
+    _f64_dev(sqnorms, dev, torch, "sqnorms", 1)
+    _check(load_library().zb_adamw_step(param.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), param.numel(),
+                                        int(frozen_tail), sqnorms.data_ptr(), k, C.c_float(max_grad_norm),
+                                        C.c_float(lr), float(beta1), float(beta2), C.c_float(eps),
+                                        C.c_float(weight_decay), int(step), _stream(torch, dev)))
+
+
+def _host(a, dtype, name, writable=False):
+    """A contiguous numpy view of a CPU tensor or numpy array (no copy: the twins write in place)."""
+    import numpy as np  # noqa: PLC0415
+
+    if hasattr(a, "detach"):
+        if a.device.type != "cpu":
+            raise ZbError(f"{name}: the host twins take CPU tensors or numpy arrays")
+        a = a.detach().numpy()
+    if not isinstance(a, np.ndarray) or a.dtype != dtype or not a.flags.c_contiguous or (writable and not a.flags.writeable):
+        raise ZbError(f"{name} must be a contiguous {np.dtype(dtype).name} array")
+    return a
+
+
+def ppo_loss_grad_host(log_prob, old_log_prob, advantages, values, old_values, value_targets,
+                       total: float | None = None, clip_param: float = _CLIP_PARAM,
+                       value_loss_coef: float = _VALUE_LOSS_COEF,
+                       use_clipped_value_loss: bool = _USE_CLIPPED_VALUE_LOSS, log_clip_value: float = _LOG_CLIP_VALUE):
+    """zb_ppo_loss_host: ppo_loss_grad on the CPU (numpy in, numpy out), the kernels' bit reference."""
+    import numpy as np  # noqa: PLC0415
+
+    lp = _host(log_prob, np.float32, "log_prob")
+    if lp.ndim != 3 or lp.shape[2] != JOINTS:
+        raise ZbError(f"log_prob must be [T, n, {JOINTS}]")
+    T, n, _ = lp.shape
+    olp = _host(old_log_prob, np.float32, "old_log_prob")
+    rest = [_host(x, np.float32, nm) for nm, x in (("advantages", advantages), ("values", values),
+                                                    ("old_values", old_values), ("value_targets", value_targets))]
+    if olp.shape != lp.shape or any(x.shape != (T, n) for x in rest):
+        raise ZbError(f"shapes must be [{T}, {n}, {JOINTS}] and [{T}, {n}]")
+    d_lp, d_v, sums = np.empty((T, n, JOINTS), np.float32), np.empty((T, n), np.float32), np.empty(4, np.float64)
+    _check(load_library().zb_ppo_loss_host(lp.ctypes.data, olp.ctypes.data, *(x.ctypes.data for x in rest), T, n,
+                                           float(T * n if total is None else total), C.c_float(clip_param),
+                                           C.c_float(value_loss_coef), 1 if use_clipped_value_loss else 0,
+                                           C.c_float(log_clip_value), d_lp.ctypes.data, d_v.ctypes.data,
+                                           sums.ctypes.data))
+    return d_lp, d_v, sums
+
+
+def grad_sqnorm_host(grad) -> float:
+    """zb_grad_sqnorm_host: the same tree on the CPU."""
+    import numpy as np  # noqa: PLC0415
+
+    g = _host(grad, np.float32, "grad")
+    out = np.empty(1, np.float64)
+    _check(load_library().zb_grad_sqnorm_host(g.ctypes.data, g.size, out.ctypes.data))
+    return float(out[0])
+
+
+def adamw_step_host(param, grad, m, v, sqnorms, step: int, lr: float, max_grad_norm: float = 0.0,
+                    weight_decay: float = 0.0, frozen_tail: int = 0, beta1: float = ADAM_BETA1,
+                    beta2: float = ADAM_BETA2, eps: float = ADAM_EPS) -> None:
+    """zb_adamw_step_host: adamw_step on the CPU, in place on param, m, v."""
+    import numpy as np  # noqa: PLC0415
+
+    p, mm, vv = (_host(x, np.float32, nm, writable=True) for nm, x in (("param", param), ("m", m), ("v", v)))
+    g = _host(grad, np.float32, "grad")
+    sq = np.ascontiguousarray(np.asarray(sqnorms, dtype=np.float64).reshape(-1))
+    if not (g.size == mm.size == vv.size == p.size):
+        raise ZbError(f"grad, m and v must hold {p.size} elements")
+    _check(load_library().zb_adamw_step_host(p.ctypes.data, g.ctypes.data, mm.ctypes.data, vv.ctypes.data, p.size,
+                                             int(frozen_tail), sq.ctypes.data, sq.size, C.c_float(max_grad_norm),
+                                             C.c_float(lr), float(beta1), float(beta2), C.c_float(eps),
+                                             C.c_float(weight_decay), int(step)))

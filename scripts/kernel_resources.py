@@ -2,6 +2,7 @@
 (-Rpass-analysis=kernel-resource-usage), one line per kernel. CPU only (cross-compiles).
 
     python scripts/kernel_resources.py [extra hipcc flags]
+    python scripts/kernel_resources.py zb_learner.hip [extra hipcc flags]   # an IEEE unit (csrc/Makefile PPO_FLAGS)
 """
 import re
 import subprocess
@@ -10,10 +11,13 @@ import os
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ksim-gym-zbot_amd", "csrc")
+args = sys.argv[1:]
+unit = args.pop(0) if args and args[0].endswith(".hip") else "zb_engine.hip"
+relaxed = ["-fno-signed-zeros", "-freciprocal-math", "-fapprox-func", "-fno-slp-vectorize"] if unit == "zb_engine.hip" else []
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"),
-       "-fno-signed-zeros", "-freciprocal-math", "-fno-math-errno", "-fapprox-func", "-fno-slp-vectorize",
-       "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/zb_engine_res.o", os.path.join(CSRC, "zb_engine.hip"),
-       *sys.argv[1:]]
+       "-fno-math-errno", *relaxed,
+       "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/zb_engine_res.o", os.path.join(CSRC, unit),
+       *args]
 err = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, rows = None, {}
 for line in err.splitlines():
