@@ -698,7 +698,24 @@ struct Ctx {
   uint32_t rmb;
   int dk0;          /* index of dof l within its body's joint (free joint: 0..5) */
   int dfree;        /* dof l belongs to a free joint */
+  /* The pointer-jumping schedules of kinematics(), subtree_sum() and dof_prefix6(): the lane each
+     round pulls from, 5 bits per round. They depend on the tree alone, so make_ctx() walks the
+     links once per launch instead of every round of every call pulling its next pointer and live
+     flag through the LDS crossbar. pjb: bits 0-14 kinematics' ancestor per round (0, the world:
+     done), bits 15-29 subtree_sum's chain successor per round (the lane itself: done). pjd:
+     dof_prefix6's ancestor dof per round (the lane itself: done). */
+  uint32_t pjb, pjd;
 };
+/* rounds of the schedules in Ctx::pjb / pjd: span = 1, 2, 4, .. below the loop bound */
+constexpr int pj_rounds(int bound) {
+  int r = 0;
+  for (int span = 1; span < bound; span <<= 1) r++;
+  return r;
+}
+constexpr int PJ_KIN = pj_rounds(MAXBD), PJ_SUB = pj_rounds(MAXBD - 1), PJ_DOF = pj_rounds(MAXDD);
+static_assert(TEAM == 32 && 5 * (PJ_KIN + PJ_SUB) <= 32 && 5 * PJ_DOF <= 32, "5-bit lanes, one word each");
+/* round r's lane of a schedule word (one bit-field extract) */
+__device__ __forceinline__ int pj_lane(uint32_t w, int r) { return (int)((w >> (5 * r)) & 31u); }
 
 
 /* a 2-bit half mask of Ctx::rmb as the 32-row mask */
@@ -807,6 +824,7 @@ __device__ __forceinline__ void st_row(gfloat_t* p, const float v[CAP]) {
  * frame of the ancestor its transform is currently relative to, doubling the
  * covered depth each round: ceil(log2(depth)) rounds instead of one pass per
  * tree level. The floating base is absolute from the start. */
+template <bool SD = false>
 __device__ __forceinline__ void kinematics(const Ctx& c, const EnvS& s, const LaneS& ls, BodyK& B) {
   MP m = c.m;
   const int b = c.l;
@@ -815,7 +833,8 @@ __device__ __forceinline__ void kinematics(const Ctx& c, const EnvS& s, const La
   float qrel_dof = ls.q - c.L->par[P_Q0][c.l];
   float ang = tsh(qrel_dof, c.bdofadr < 0 ? 0 : c.bdofadr);
   float p[3] = {0.f, 0.f, 0.f}, q[4] = {1.f, 0.f, 0.f, 0.f};
-  int anc = 0; /* frame the transform is relative to (0: world) */
+  const uint32_t pj = SD ? (uint32_t)vopq((int)c.pjb) : 0u;
+  int anc0 = 0; /* !SD: the frame the transform is relative to (0: world), followed round by round */
   if (isb) {
     if (c.bjt == ZB_JNT_FREE) {
 #pragma unroll
@@ -842,25 +861,47 @@ __device__ __forceinline__ void kinematics(const Ctx& c, const EnvS& s, const La
 #pragma unroll
         for (int k = 0; k < 4; k++) q[k] = qn[k];
       }
-      anc = c.bpar;
+      anc0 = c.bpar;
     }
   }
-  for (int span = 1; span < MAXBD; span <<= 1) {
-    float ap[3], aq[4];
+  if constexpr (SD) {
 #pragma unroll
-    for (int k = 0; k < 3; k++) ap[k] = tsh(p[k], anc);
+    for (int r = 0; r < PJ_KIN; r++) {
+      const int anc = pj_lane(pj, r); /* frame the transform is relative to (0, the world: done) */
+      float ap[3], aq[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) aq[k] = tsh(q[k], anc);
-    const int aa = tshi(anc, anc);
-    if (anc != 0) {
-      float t[3], qq[4];
-      quat_rotate(t, aq, p);
+      for (int k = 0; k < 3; k++) ap[k] = tsh(p[k], anc);
 #pragma unroll
-      for (int k = 0; k < 3; k++) p[k] = ap[k] + t[k];
-      quat_mul(qq, aq, q);
+      for (int k = 0; k < 4; k++) aq[k] = tsh(q[k], anc);
+      if (anc != 0) {
+        float t[3], qq[4];
+        quat_rotate(t, aq, p);
 #pragma unroll
-      for (int k = 0; k < 4; k++) q[k] = qq[k];
-      anc = aa;
+        for (int k = 0; k < 3; k++) p[k] = ap[k] + t[k];
+        quat_mul(qq, aq, q);
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = qq[k];
+      }
+    }
+  } else {
+    int anc = anc0;
+    for (int span = 1; span < MAXBD; span <<= 1) {
+      float ap[3], aq[4];
+#pragma unroll
+      for (int k = 0; k < 3; k++) ap[k] = tsh(p[k], anc);
+#pragma unroll
+      for (int k = 0; k < 4; k++) aq[k] = tsh(q[k], anc);
+      const int aa = tshi(anc, anc);
+      if (anc != 0) {
+        float t[3], qq[4];
+        quat_rotate(t, aq, p);
+#pragma unroll
+        for (int k = 0; k < 3; k++) p[k] = ap[k] + t[k];
+        quat_mul(qq, aq, q);
+#pragma unroll
+        for (int k = 0; k < 4; k++) q[k] = qq[k];
+        anc = aa;
+      }
     }
   }
   if (isb && c.bjt != ZB_JNT_FREE) quat_normalize(q);
@@ -877,23 +918,38 @@ __device__ __forceinline__ void kinematics(const Ctx& c, const EnvS& s, const La
  * branching body (the floating base, body 1; checked by zb_create), so below
  * it every subtree is a chain suffix: pointer jumping along the child links
  * sums the chains in log2(length) rounds, then the base gathers its children. */
-template <int K>
+template <int K, bool SD = false>
 __device__ __forceinline__ void subtree_sum(const Ctx& c, float v[K]) {
   EnvL* L = c.L;
-  const bool chain = c.l >= 2 && c.l < NB && c.nch == 1;
-  int nxt = chain ? childof(c, 0) : c.l;
-  bool live = chain;
-  for (int span = 1; span < MAXBD - 1; span <<= 1) {
-    float w[K];
+  if constexpr (SD) {
+    const uint32_t pj = (uint32_t)vopq((int)c.pjb) >> (5 * PJ_KIN);
 #pragma unroll
-    for (int i = 0; i < K; i++) w[i] = tsh(v[i], nxt);
-    const int nn = tshi(nxt, nxt);
-    const bool nl = tshi(live ? 1 : 0, nxt) != 0;
-    if (live) {
+    for (int r = 0; r < PJ_SUB; r++) {
+      const int nxt = pj_lane(pj, r); /* the chain's next unsummed body (the lane itself: done) */
+      float w[K];
 #pragma unroll
-      for (int i = 0; i < K; i++) v[i] += w[i];
-      nxt = nn;
-      live = nl;
+      for (int i = 0; i < K; i++) w[i] = tsh(v[i], nxt);
+      if (nxt != c.l) {
+#pragma unroll
+        for (int i = 0; i < K; i++) v[i] += w[i];
+      }
+    }
+  } else {
+    const bool chain = c.l >= 2 && c.l < NB && c.nch == 1;
+    int nxt = chain ? childof(c, 0) : c.l;
+    bool live = chain;
+    for (int span = 1; span < MAXBD - 1; span <<= 1) {
+      float w[K];
+#pragma unroll
+      for (int i = 0; i < K; i++) w[i] = tsh(v[i], nxt);
+      const int nn = tshi(nxt, nxt);
+      const bool nl = tshi(live ? 1 : 0, nxt) != 0;
+      if (live) {
+#pragma unroll
+        for (int i = 0; i < K; i++) v[i] += w[i];
+        nxt = nn;
+        live = nl;
+      }
     }
   }
 #pragma unroll
@@ -914,6 +970,7 @@ __device__ __forceinline__ void subtree_sum(const Ctx& c, float v[K]) {
 
 /* ------------------------------ mass matrix -------------------------------- */
 /* com, cinert (lane b), cdof (lane j -> LDS), crb, M rows (LDS + return) */
+template <bool SD = false>
 __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const LaneS& ls, BodyK& B, float cm[3]) {
   const int ddep = vopq(c.ddep);
   MP m = c.m;
@@ -923,7 +980,8 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
   const int bb = isbody ? b : 0;
   const float mscale = keepf(c.L->par[P_MSCALE][c.l]);
   const float bmass = keepf(m->body_mass[bb][0]);
-  float mass = isbody ? bmass * mscale : 0.f;
+  /* SD: mscale is zero off the bodies (load_params); rounded: the product stays out of the team sum's adds */
+  float mass = SD ? rounded(bmass * mscale) : (isbody ? bmass * mscale : 0.f);
   float xipos[3], Ri[9];
   {
     float ip[3] = {m->body_ipos[isbody ? b : 0][0], m->body_ipos[isbody ? b : 0][1], m->body_ipos[isbody ? b : 0][2]}, t[3];
@@ -947,7 +1005,7 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
 #pragma unroll
     for (int k = 0; k < 3; k++) {
       const float bi = keepf(m->body_inertia[bb][k]);
-      in[k] = isbody ? bi * mscale : 0.f;
+      in[k] = SD ? bi * mscale : (isbody ? bi * mscale : 0.f);
     }
     float dif[3] = {xipos[0] - cm[0], xipos[1] - cm[1], xipos[2] - cm[2]};
     float I[9];
@@ -981,7 +1039,8 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
     quat2mat(R, xqs);
 #pragma unroll
     for (int k = 0; k < 3; k++) xp[k] = tsh(B.xp[k], bj);
-    /* every lane, the non-dof ones storing zero rows (read as zero by com_vel / com_acc) */
+    /* SD: the dof lanes, the others keep the zero rows make_ctx stored; else every lane, the non-dof
+       ones storing zero rows (read as zero by com_vel / com_acc) */
     {
       /* branch-free over the dof kinds (the task's dofs are the free joint's 6 and
          hinges): the motion axis in the body frame is jnt_axis for a hinge and unit
@@ -1007,8 +1066,15 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
         cd[3 + i] = trans ? (k == i ? 1.f : 0.f) : cr[i];
       }
       const bool isd = j < NV;
+      if constexpr (SD) {
+        if (isd) {
 #pragma unroll
-      for (int i = 0; i < 6; i++) L->cdof[j][i] = isd ? cd[i] : 0.f;
+          for (int i = 0; i < 6; i++) L->cdof[j][i] = cd[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < 6; i++) L->cdof[j][i] = isd ? cd[i] : 0.f;
+      }
     }
   }
   /* crb = subtree sums of cinert */
@@ -1016,7 +1082,7 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
 #pragma unroll
   for (int k = 0; k < 10; k++) crb[k] = ci[k];
   tsync();
-  subtree_sum<10>(c, crb);
+  subtree_sum<10, SD>(c, crb);
   /* M rows: M(j, anc_e(j)) = cdof_anc . (crb_body(j) * cdof_j), packed storage */
   {
     const int j = c.l;
@@ -1641,27 +1707,49 @@ __device__ __forceinline__ float mul_m_dot(const Ctx& c, const Rows& r, const fl
 /* inclusive prefix sums of per-dof 6-vectors along the dof tree (root ->
  * dof), by pointer jumping over the parent links: ceil(log2(depth)) rounds of
  * cross-lane pulls instead of one ancestor gather per depth */
+template <bool SD = false>
 __device__ __forceinline__ void dof_prefix6(const Ctx& c, float P[6]) {
-  const int ddep = vopq(c.ddep);
-  bool live = c.l < NV && ddep > 0;
-  int ptr = live ? anc_lin(c.chd, ddep - 1) : c.l;
-  for (int span = 1; span < MAXDD; span <<= 1) {
-    float w[6];
+  if constexpr (SD) {
+    const uint32_t pj = (uint32_t)vopq((int)c.pjd);
 #pragma unroll
-    for (int k = 0; k < 6; k++) w[k] = tsh(P[k], ptr);
-    const int nptr = tshi(ptr, ptr);
-    const bool nlive = tshi(live ? 1 : 0, ptr) != 0;
-    if (live) {
+    for (int r = 0; r < PJ_DOF; r++) {
+      const int ptr = pj_lane(pj, r); /* the nearest ancestor dof not yet in the prefix (the lane itself: done) */
+      float w[6];
 #pragma unroll
-      for (int k = 0; k < 6; k++) P[k] += w[k];
-      ptr = nptr;
-      live = nlive;
+      for (int k = 0; k < 6; k++) w[k] = tsh(P[k], ptr);
+      if (ptr != c.l) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) P[k] += w[k];
+      }
+    }
+  } else {
+    const int ddep = vopq(c.ddep);
+    bool live = c.l < NV && ddep > 0;
+    int ptr = live ? anc_lin(c.chd, ddep - 1) : c.l;
+    for (int span = 1; span < MAXDD; span <<= 1) {
+      float w[6];
+#pragma unroll
+      for (int k = 0; k < 6; k++) w[k] = tsh(P[k], ptr);
+      const int nptr = tshi(ptr, ptr);
+      const bool nlive = tshi(live ? 1 : 0, ptr) != 0;
+      if (live) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) P[k] += w[k];
+        ptr = nptr;
+        live = nlive;
+      }
     }
   }
 }
 
+/* The last lane of a team is neither a dof nor a body: its cdof row, qvel and qacc are zeros, so
+   its per-dof 6-vectors and their prefix (dof_prefix6 leaves it alone) are exact +0. A lane that
+   wants zeros from a prefix pull reads them there instead of selecting them afterwards. */
+constexpr int ZLANE = TEAM - 1;
+static_assert(NV <= ZLANE && NB <= ZLANE, "lane ZLANE holds zeros");
 /* mj_comVel: cvel (lane b, in B.cv) and cdof_dot (lane j, returned).
    Requires the dof lanes' qvel in ls_v. */
+template <bool SD = false>
 __device__ __forceinline__ void com_vel(const Ctx& c, BodyK& B, float qv, float cdd[6]) {
   const int ddep = vopq(c.ddep);
   EnvL* L = c.L;
@@ -1674,56 +1762,80 @@ __device__ __forceinline__ void com_vel(const Ctx& c, BodyK& B, float qv, float 
   float P[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) P[k] = cd[k] * qv;
-  dof_prefix6(c, P);
+  dof_prefix6<SD>(c, P);
   /* velocity before this dof's own contribution: the parent's prefix for a
      hinge, the translational part (dof 2) for the free joint's rotations */
   const bool isfree = c.dfree;
   const int k0 = c.dk0;
-  const int par = (isd && ddep > 0) ? anc_lin(c.chd, ddep - 1) : j;
+  /* the parent dof (SD: round 0 of dof_prefix6's schedule; the lane itself: none) */
+  int par;
+  if constexpr (SD) par = pj_lane((uint32_t)vopq((int)c.pjd), 0);
+  else par = (isd && ddep > 0) ? anc_lin(c.chd, ddep - 1) : j;
   const int src = (isfree && k0 >= 3) ? 2 : par; /* one pull per component */
+  /* SD: read only by the lanes below, the free joint's rotations and the hinges, which all have
+     a parent dof, so no lane needs a zero in place of the pull */
   float before[6];
 #pragma unroll
   for (int k = 0; k < 6; k++) {
     const float pp = tsh(P[k], src);
-    before[k] = ddep > 0 ? pp : 0.f;
+    if constexpr (SD) before[k] = pp;
+    else before[k] = ddep > 0 ? pp : 0.f;
   }
 #pragma unroll
   for (int k = 0; k < 6; k++) cdd[k] = 0.f;
   if (isd && !(isfree && k0 < 3)) cross_motion(cdd, before, cd);
-  /* body velocity = prefix at the body's deepest dof */
-  const int bl = (c.l < NB && c.blast >= 0) ? c.blast : 0;
+  /* body velocity = prefix at the body's deepest dof (SD: a lane without one pulls lane ZLANE's zeros) */
+  if constexpr (SD) {
+    const int bl = (c.l < NB && c.blast >= 0) ? c.blast : ZLANE;
 #pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const float v = tsh(P[k], bl);
-    B.cv[k] = (c.l < NB && c.blast >= 0) ? v : 0.f;
+    for (int k = 0; k < 6; k++) B.cv[k] = tsh(P[k], bl);
+  } else {
+    const int bl = (c.l < NB && c.blast >= 0) ? c.blast : 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const float v = tsh(P[k], bl);
+      B.cv[k] = (c.l < NB && c.blast >= 0) ? v : 0.f;
+    }
   }
 }
 
 /* cacc per body (lane b): -g + prefix of cdof_dot*qvel (+ cdof*qacc) */
+template <bool SD = false>
 __device__ __forceinline__ void com_acc(const Ctx& c, const float cdd[6], float qv, float qa, float ca[6],
                                         bool with_acc) {
   MP m = c.m;
   EnvL* L = c.L;
   const int j = c.l;
   const bool isd = j < NV;
+  /* SD: cdd and qv are zero past the dofs; rounded: the product stays out of the adds that take it */
   float P[6];
 #pragma unroll
-  for (int k = 0; k < 6; k++) P[k] = isd ? cdd[k] * qv : 0.f;
+  for (int k = 0; k < 6; k++) {
+    if constexpr (SD) P[k] = rounded(cdd[k] * qv);
+    else P[k] = isd ? cdd[k] * qv : 0.f;
+  }
   if (with_acc) {
 #pragma unroll
     for (int k = 0; k < 6; k++) P[k] += L->cdof[j][k] * qa; /* zero rows past the dofs */
   }
-  dof_prefix6(c, P);
+  dof_prefix6<SD>(c, P);
   const float g[6] = {0.f, 0.f, 0.f, -m->gravity[0], -m->gravity[1], -m->gravity[2]};
-  const int bl = (c.l < NB && c.blast >= 0) ? c.blast : 0;
+  if constexpr (SD) {
+    const int bl = (c.l < NB && c.blast >= 0) ? c.blast : ZLANE; /* no dof above the body: lane ZLANE's zeros */
 #pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const float v = tsh(P[k], bl);
-    ca[k] = g[k] + ((c.l < NB && c.blast >= 0) ? v : 0.f);
+    for (int k = 0; k < 6; k++) ca[k] = g[k] + tsh(P[k], bl);
+  } else {
+    const int bl = (c.l < NB && c.blast >= 0) ? c.blast : 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+      const float v = tsh(P[k], bl);
+      ca[k] = g[k] + ((c.l < NB && c.blast >= 0) ? v : 0.f);
+    }
   }
 }
 
 /* body force cfrc (lane b) -> subtree sums in sub[] ; returns dof projection cdof_j . sub[body(j)] */
+template <bool SD = false>
 __device__ __forceinline__ float rne_project(const Ctx& c, const BodyK& B, const float ca[6], const float fext[6]) {
   EnvL* L = c.L;
   float f[6];
@@ -1740,7 +1852,7 @@ __device__ __forceinline__ float rne_project(const Ctx& c, const BodyK& B, const
 #pragma unroll
     for (int k = 0; k < 6; k++) f[k] = 0.f;
   }
-  subtree_sum<6>(c, f);
+  subtree_sum<6, SD>(c, f);
   float r = 0.f;
   if (c.l < NV) {
     float cd[6], fs[6];
@@ -3696,16 +3808,20 @@ __device__ __forceinline__ void feetech(const Ctx& c, LaneS& ls) {
 /* ------------------------------- full forward ------------------------------ */
 /* mj_forward (+ sensors if requested). Leaves qacc in ls.qacc, kinematics in B. */
 /* FQ: the caller reads ls.fq after a pass without sensors (implicit_damping of the ED kernels) */
-template <int SOLVER, int XG, bool FQ = true>
+/* SD: the trimmed forms of the once-per-substep phases ("the smooth phases'
+   VALU diet"): the pointer-jumping schedules from Ctx::pjb / pjd, masks folded into data (the mass
+   scale, the cdof rows, lane ZLANE's zeros).
+   Bit-identical to the forms they replace, which the other instantiations keep. */
+template <int SOLVER, int XG, bool FQ = true, bool SD = false>
 __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, BodyK& B, Rows& r, bool with_sensors,
                                         Sensors& sen, int& iters) {
   MP m = c.m;
   EnvL* L = c.L;
   STAMP(S_ENTRY);
-  kinematics(c, s, ls, B);
+  kinematics<SD>(c, s, ls, B);
   STAMP(S_KIN);
   float cm[3];
-  com_crb_m(c, s, ls, B, cm);
+  com_crb_m<SD>(c, s, ls, B, cm);
   STAMP(S_CRB);
   /* factor M (copy of rows) */
   float X[CAP];
@@ -3717,10 +3833,10 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   tsync();
   const float qv = c.l < NV ? ls.v : 0.f;
   float cdd[6];
-  com_vel(c, B, qv, cdd);
+  com_vel<SD>(c, B, qv, cdd);
   float ca[6], zero6[6] = {0, 0, 0, 0, 0, 0};
-  com_acc(c, cdd, qv, 0.f, ca, false);
-  float bias = rne_project(c, B, ca, zero6);
+  com_acc<SD>(c, cdd, qv, 0.f, ca, false);
+  float bias = rne_project<SD>(c, B, ca, zero6);
   /* actuation + passive -> qfrc_smooth, qacc_smooth */
   float act = 0.f;
   if (c.act >= 0) {
@@ -3851,11 +3967,11 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   {
     BodyK B2 = B; /* cdof_dot again (not kept in registers through the solver) */
     float cdd2[6];
-    com_vel(c, B2, qv, cdd2);
-    com_acc(c, cdd2, qv, ls.qacc, cacc, true);
+    com_vel<SD>(c, B2, qv, cdd2);
+    com_acc<SD>(c, cdd2, qv, ls.qacc, cacc, true);
   }
   /* cfrc_int subtree sums (in sub[]) */
-  (void)rne_project(c, B, cacc, fext);
+  (void)rne_project<SD>(c, B, cacc, fext);
   /* imu site: framequat, gyro, accelerometer */
   {
     int sb = m->site_body[m->site_imu];
@@ -3950,6 +4066,8 @@ __device__ __forceinline__ void integrate(const Ctx& c, EnvS& s, LaneS& ls, floa
 }
 
 /* --------------------------- env-level (ksim) logic ------------------------- */
+/* SD: also what forward()'s trimmed smooth phases read (the mass scale zero off the bodies) */
+template <bool SD = false>
 __device__ __forceinline__ void load_params(const Ctx& c, EnvS& s, LaneS& ls, const float* rnd) {
   MP m = c.m;
   const bool rz = (c.cfg->flags & ZB_F_RANDOMIZE) && rnd;
@@ -3961,7 +4079,10 @@ __device__ __forceinline__ void load_params(const Ctx& c, EnvS& s, LaneS& ls, co
     floss = m->dof_frictionloss[l] * (rz ? rnd[ZB_R_FRICTION + l] : 1.f);
     if (c.qadr >= 0) q0 = m->qpos0[c.qadr] + ((rz && c.act >= 0) ? rnd[ZB_R_QPOS0 + c.act] : 0.f);
   }
-  c.L->par[P_MSCALE][l] = (rz && l < NB) ? rnd[ZB_R_MASS + l] : 1.f;
+  /* SD: zero off the bodies (the world, the lanes past them), so that com_crb_m's masses and
+     inertias there are exact zeros without a mask */
+  if constexpr (SD) c.L->par[P_MSCALE][l] = (l >= 1 && l < NB) ? (rz ? rnd[ZB_R_MASS + l] : 1.f) : 0.f;
+  else c.L->par[P_MSCALE][l] = (rz && l < NB) ? rnd[ZB_R_MASS + l] : 1.f;
   c.L->par[P_ARM][l] = arm;
   c.L->par[P_DAMP][l] = damp;
   c.L->par[P_FLOSS][l] = floss;
@@ -4310,6 +4431,7 @@ __device__ __forceinline__ void store_state(const Ctx& c, const EnvS& s, const L
 }
 
 /* ksim reset (train.py:1471-1476); the caller then runs mjx.forward (forward()) */
+template <bool SD = false>
 __device__ __forceinline__ void reset_prepare(const Ctx& c, EnvS& s, LaneS& ls, float* rnd) {
   MP m = c.m;
   CP cfg = c.cfg;
@@ -4320,7 +4442,7 @@ __device__ __forceinline__ void reset_prepare(const Ctx& c, EnvS& s, LaneS& ls, 
     tsync();
     __threadfence_block();
   }
-  load_params(c, s, ls, rnd);
+  load_params<SD>(c, s, ls, rnd);
   for (int k = 0; k < 3; k++) s.bp[k] = m->qpos0[k];
   for (int k = 0; k < 4; k++) s.bq[k] = m->qpos0[3 + k];
   ls.v = 0.f;
@@ -4369,6 +4491,8 @@ __device__ __forceinline__ void push_event(const Ctx& c, EnvS& s, LaneS& ls, flo
 }
 
 /* ---------------------------- per-team context ------------------------------ */
+/* SD: also what forward()'s trimmed smooth phases read (Ctx::pjb / pjd, zero cdof rows past the dofs) */
+template <bool SD = false>
 __device__ __forceinline__ void make_ctx(Ctx& c, const ZbModel* m, const ZbEnvConfig* cfg, const int32_t* topo,
                                          EnvL* L, uint64_t seed, uint32_t env) {
   static_assert(TOPO_NROOT == NROOT && TOPO_NGEOM == NGEOM && TOPO_MAXBD == MAXBD && TOPO_LANES == TEAM,
@@ -4407,14 +4531,54 @@ __device__ __forceinline__ void make_ctx(Ctx& c, const ZbModel* m, const ZbEnvCo
   c.chd = t[TP_CHD * TEAM];
   c.cps = t[TP_CPS * TEAM];
   c.cln = t[TP_CLN * TEAM];
+  c.pjb = c.pjd = 0u;
+  if constexpr (SD) {
+    /* the pointer-jumping schedules (Ctx::pjb, pjd): the rounds' pulls as the functions ran them,
+       on the links alone. Every lane of the wave is active here */
+    uint32_t wb = 0u, wd = 0u;
+    int anc = (l >= 1 && l < NB && c.bjt != ZB_JNT_FREE) ? c.bpar : 0;
+    for (int r = 0; r < PJ_KIN; r++) {
+      wb |= (uint32_t)anc << (5 * r);
+      const int aa = tshi(anc, anc);
+      if (anc != 0) anc = aa;
+    }
+    bool live = l >= 2 && l < NB && c.nch == 1;
+    int nxt = live ? childof(c, 0) : l;
+    for (int r = 0; r < PJ_SUB; r++) {
+      wb |= (uint32_t)(live ? nxt : l) << (5 * (PJ_KIN + r));
+      const int nn = tshi(nxt, nxt);
+      const bool nl = tshi(live ? 1 : 0, nxt) != 0;
+      if (live) {
+        nxt = nn;
+        live = nl;
+      }
+    }
+    live = l < NV && c.ddep > 0;
+    int ptr = live ? anc_lin(c.chd, c.ddep - 1) : l;
+    for (int r = 0; r < PJ_DOF; r++) {
+      wd |= (uint32_t)(live ? ptr : l) << (5 * r);
+      const int np = tshi(ptr, ptr);
+      const bool nl = tshi(live ? 1 : 0, ptr) != 0;
+      if (live) {
+        ptr = np;
+        live = nl;
+      }
+    }
+    c.pjb = wb;
+    c.pjd = wd;
+  }
   if (l >= NV) {
-    /* non-dof lanes: zero factor and mass rows (row 31 is the zero row that masked
+    /* non-dof lanes: zero factor, mass and cdof rows (row 31 is the zero row that masked
        gathers point at; kernels never write these rows afterwards) */
     float z[CAP];
 #pragma unroll
     for (int e = 0; e < CAP; e++) z[e] = 0.f;
     st_row(&L->L[l][0], z);
     st_row(&L->M[l][0], z);
+    if constexpr (SD) {
+#pragma unroll
+      for (int k = 0; k < 6; k++) L->cdof[l][k] = 0.f; /* com_crb_m<SD> writes the dof lanes' rows only */
+    }
   }
 }
 
@@ -4426,6 +4590,13 @@ __device__ __forceinline__ void make_ctx(Ctx& c, const ZbModel* m, const ZbEnvCo
 #ifndef ZB_WAVES_PER_EU
 #define ZB_WAVES_PER_EU 2
 #endif
+/* The step kernels that take forward()'s trimmed smooth phases (SD): every instantiation whose
+   vector-register spills do not rise with them (DESIGN.md section 10 has the counts). The others,
+   the sole-pair kernels foremost, keep the parent's forms, as do the reset and debug kernels. */
+template <int SOLVER, int XG, bool ED>
+constexpr bool SMOOTH_DIET = SOLVER == ZB_SOLVER_CG
+                                 ? (XG == 0 || XG == 5 || (XG == 1 && !ED) || (XG == 2 && ED) || (XG == 3 && ED))
+                                 : (XG == 0 || XG == 2 || XG == 5);
 template <int SOLVER, int XG, int ED>
 __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const int team = threadIdx.x / TEAM;
@@ -4479,8 +4650,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const int ee = live ? e : a.n_envs - 1;
   const ZbModel* m = a.model;
   const ZbEnvConfig* cfg = a.cfg;
+  constexpr bool SD = SMOOTH_DIET<SOLVER, XG, ED != 0>;
   Ctx c;
-  make_ctx(c, m, cfg, a.topo, &g_lds[team], a.seed, (uint32_t)(a.env_offset + ee));
+  make_ctx<SD>(c, m, cfg, a.topo, &g_lds[team], a.seed, (uint32_t)(a.env_offset + ee));
   /* the env's second-bank rows (a team past n: the spare block n) */
   if constexpr (XG) set_xrows(c.L, a.xj + (size_t)(live ? e : a.n_envs) * XJ_STRIDE<XG>);
   /* per-env row addresses are formed where they are used, from an opaque copy of the env
@@ -4498,7 +4670,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   LaneS ls;
   if (K > 1) load_state<true>(c, s, ls, state_row());
   else load_state<false>(c, s, ls, state_row());
-  load_params(c, s, ls, rand_row());
+  load_params<SD>(c, s, ls, rand_row());
   BodyK B;
   Rows r;
   Sensors& sen = c.L->sen;
@@ -4536,7 +4708,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (!resetting && !ghost) feetech<XG>(c, ls);
       STAMP(S_FEETECH);
       int it_pass = 0;
-      forward<SOLVER, XG, ED != 0>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
+      forward<SOLVER, XG, ED != 0, SD>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
       if (!ghost) iters += it_pass;
       if (!resetting && !ghost) {
         /* wave-uniform: both teams integrate, or both run the reset / ghost pass */
@@ -4591,7 +4763,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (resetting || ghost) break;
       if (__ballot(done_reset) == 0ull) break;
       if (done_reset) {
-        reset_prepare(c, s, ls, rand_row());
+        reset_prepare<SD>(c, s, ls, rand_row());
         resetting = true;
       } else {
         ghost = true;
