@@ -18,6 +18,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "zbot_policy.h" /* the RNG purposes ZB_RNG_POLICY, ZB_RNG_SHUFFLE */
+
 #if defined(__HIPCC__)
 #define ZBF_FN __host__ __device__ static inline
 #else
@@ -164,6 +166,39 @@ ZBF_FN float zbf_normal(uint64_t seed, uint32_t purpose, uint32_t k, uint32_t en
   float s, c;
   zbf_sincos_turns(u2, &s, &c);
   return r * c;
+}
+
+/* ---- keyed permutation of [0, n): the minibatch shuffle (include/zbot_ppo.h "Minibatches") ---- */
+/* For fixed (seed, epoch, n) a bijection of [0, n), computed per index (no sort, no table; integers
+   only, so host and device agree by construction). A balanced Feistel network of 4 rounds over 2h
+   bits, h = max(4, ceil(bits(n - 1) / 2)); round r maps (L, R) -> (R, L ^ F_r(R)) with F_r(R) the
+   low h bits of the first word of zbf_rng_bits(seed, ZB_RNG_SHUFFLE, r, R, epoch), the purpose
+   declared in include/zbot_policy.h. The network permutes [0, 2^2h); values >= n are fed back in
+   until one lands below n (cycle walking: the walk follows i's cycle of that permutation, which
+   returns to i < n, so it ends). 2^2h < 4 n above the floor, i.e. about 2 walks on average. The floor h >= 4 keeps small n mixed: with 2 or 4 bits the
+   network is the identity at n = 2 and 3 and visibly non-uniform at n = 8.
+   n <= 1 returns 0; i >= n is outside the domain and is returned as it is. */
+ZBF_FN uint32_t zbf_perm_index(uint64_t seed, uint32_t epoch, uint32_t n, uint32_t i) {
+  if (n <= 1u) return 0u;
+  if (i >= n) return i;
+  int bits = 0;
+  for (uint32_t m = n - 1u; m; m >>= 1) bits++;
+  int h = (bits + 1) / 2;
+  h = h < 4 ? 4 : h; /* <= 16 */
+  const uint32_t mask = (1u << h) - 1u;
+  uint32_t x = i;
+  do {
+    uint32_t L = x >> h, R = x & mask;
+    for (uint32_t r = 0; r < 4u; r++) {
+      uint32_t a, b;
+      zbf_rng_bits(seed, ZB_RNG_SHUFFLE, r, R, epoch, &a, &b);
+      const uint32_t t = L ^ (a & mask);
+      L = R;
+      R = t;
+    }
+    x = (L << h) | R;
+  } while (x >= n);
+  return x;
 }
 
 /* ---- mixture-of-Gaussians action head of one joint (ksim MixtureOfGaussians [U]) ---- */

@@ -59,6 +59,7 @@ extern "C" {
 #define ZB_POL_EVAL 2          /* log_prob of the given actions (in) */
 
 #define ZB_RNG_POLICY 5u       /* RNG purpose of the action sample (engine uses 1-4) */
+#define ZB_RNG_SHUFFLE 6u      /* RNG purpose of the minibatch permutation (zbot_fmath.h zbf_perm_index) */
 
 typedef struct ZbPolicy ZbPolicy;
 

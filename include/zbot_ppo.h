@@ -176,6 +176,52 @@ int zb_adamw_step_host(float* param, const float* grad, float* m, float* v, size
                        const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2,
                        float eps, float weight_decay, int step);
 
+/*
+ * ---- Minibatches: the keyed permutation and the gather that cuts a minibatch ----
+ *
+ * A PPO pass visits the rollout's n envs in minibatches. With shuffling, minibatch k of pass
+ * `epoch` is positions [k batch, (k + 1) batch) of the permutation
+ *   p(i) = zbf_perm_index(seed, epoch, n, i)      (include/zbot_fmath.h; integers only, the same
+ *                                                  bits on host and device)
+ * ksim shuffles with its own RNG [U]; this law is this library's.
+ *
+ * zb_minibatch_gather moves every array of one minibatch in one launch: for every item and every
+ * t < rows, j < count
+ *   dst[t][j][:] = src[t][p(lo + j)][:]           (p the identity when shuffle == 0)
+ * The source of an item is [rows][n][row_bytes] with an explicit stride between time rows
+ * (src_t_stride_bytes >= 0: the first T rows of a [T + 1, n, 50] buffer are an item; a carry is
+ * rows = 1); the destination is dense [rows][count][row_bytes]. src == NULL zero-fills (row 0 of
+ * `reset` in a first rollout). Each item moves in the widest of 16-, 8-, 4- and 1-byte accesses
+ * that divides its row_bytes, both pointers and (with rows > 1) its stride. Sources and
+ * destinations must not overlap.
+ *
+ * `items` is a host array (read during the call, passed to the kernel by value); the pointers in
+ * it are device pointers (host pointers for zb_minibatch_gather_host). Asynchronous on `stream`,
+ * nothing allocated, nothing synchronized. Bad arguments (a null items / dst, n_items outside
+ * 1 .. ZB_GATHER_MAX_ITEMS, n < 1, lo < 0, count < 1, lo + count > n, rows < 1, row_bytes outside
+ * 1 .. ZB_GATHER_MAX_ROW_BYTES, a negative stride) return ZB_EARG and launch nothing.
+ */
+#define ZB_GATHER_MAX_ITEMS 16
+#define ZB_GATHER_MAX_ROW_BYTES (1 << 24) /* per env and time row */
+
+typedef struct ZbGatherItem {
+  const void* src;            /* [rows][n][row_bytes], time stride src_t_stride_bytes; NULL: zeros */
+  void* dst;                  /* [rows][count][row_bytes], dense */
+  int32_t rows;
+  int32_t row_bytes;
+  int64_t src_t_stride_bytes;
+} ZbGatherItem;
+
+/* perm[i] = zbf_perm_index(seed, epoch, n, i) for i < n (n >= 1). For callers and tests: the
+   gather evaluates the permutation itself. */
+int zb_minibatch_perm(uint64_t seed, uint32_t epoch, int n, int32_t* perm, void* stream);
+int zb_minibatch_perm_host(uint64_t seed, uint32_t epoch, int n, int32_t* perm);
+
+int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                        uint64_t seed, uint32_t epoch, void* stream);
+int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                             uint64_t seed, uint32_t epoch);
+
 #ifdef __cplusplus
 }
 #endif

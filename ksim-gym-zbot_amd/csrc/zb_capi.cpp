@@ -506,6 +506,32 @@ int zb_adamw_step(float* param, const float* grad, float* m, float* v, size_t co
   return ZB_OK;
 }
 
+/* ---- minibatches: the permutation and the gather (include/zbot_ppo.h "Minibatches") ---- */
+
+int zb_minibatch_perm(uint64_t seed, uint32_t epoch, int n, int32_t* perm, void* stream) {
+  if (!perm || n < 1) return fail(ZB_EARG, "zb_minibatch_perm: null perm or n = %d", n);
+  hipError_t e = zb::launch_minibatch_perm(seed, epoch, n, perm, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_minibatch_perm launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                        uint64_t seed, uint32_t epoch, void* stream) {
+  zb::GatherArgs a;
+  memset(&a, 0, sizeof a);
+  if (int rc = zb::check_gather_args("zb_minibatch_gather", items, n_items, n, lo, count, a.it)) return rc;
+  a.n_items = n_items;
+  a.n = n;
+  a.lo = lo;
+  a.count = count;
+  a.shuffle = shuffle ? 1 : 0;
+  a.epoch = epoch;
+  a.seed = seed;
+  hipError_t e = zb::launch_minibatch_gather(a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_minibatch_gather launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
 /* ---- GRU policy / value networks (include/zbot_policy.h) ---- */
 
 struct ZbPolicy {

@@ -2,7 +2,9 @@
  * zb_host.cpp — the host-only half of the C ABI (include/zbot.h): the error string, the
  * train.py default configuration, model / config validation and the per-lane team topology;
  * and the learner's host twins (include/zbot_ppo.h "Learner": zb_ppo_loss_host,
- * zb_grad_sqnorm_host, zb_adamw_step_host), the CPU bit reference of csrc/zb_learner.hip.
+ * zb_grad_sqnorm_host, zb_adamw_step_host), the CPU bit reference of csrc/zb_learner.hip; and
+ * the minibatch twins ("Minibatches": zb_minibatch_perm_host, zb_minibatch_gather_host), that of
+ * csrc/zb_minibatch.hip.
  * Plain C++ (no HIP): the product library links it, and csrc/sanitize.mk builds it with the host
  * sanitizers for tests/test_sanitizers.py.
  */
@@ -17,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "zbot_fmath.h"
 #include "zbot_learner_math.h"
 #include "zbot_ppo.h"
 
@@ -364,6 +367,35 @@ int check_adamw_args(const char* what, const void* param, const void* grad, cons
   return ZB_OK;
 }
 
+int check_gather_args(const char* what, const ZbGatherItem* items, int n_items, int n, int lo, int count,
+                      GatherItemDev* out) {
+  if (!items) return fail(ZB_EARG, "%s: null items", what);
+  if (n_items < 1 || n_items > ZB_GATHER_MAX_ITEMS)
+    return fail(ZB_EARG, "%s: n_items = %d (1 to %d)", what, n_items, ZB_GATHER_MAX_ITEMS);
+  if (n < 1 || lo < 0 || count < 1 || (long long)lo + (long long)count > (long long)n)
+    return fail(ZB_EARG, "%s: envs [%d, %d + %d) of n = %d", what, lo, lo, count, n);
+  for (int k = 0; k < n_items; k++) {
+    const ZbGatherItem& it = items[k];
+    if (!it.dst) return fail(ZB_EARG, "%s: item %d: null dst", what, k);
+    if (it.rows < 1 || it.row_bytes < 1 || it.row_bytes > ZB_GATHER_MAX_ROW_BYTES)
+      return fail(ZB_EARG, "%s: item %d: rows = %d, row_bytes = %d", what, k, it.rows, it.row_bytes);
+    if (it.src_t_stride_bytes < 0) return fail(ZB_EARG, "%s: item %d: negative stride", what, k);
+    uintptr_t bits = (uintptr_t)it.row_bytes | (uintptr_t)it.dst;
+    if (it.src) {
+      bits |= (uintptr_t)it.src;
+      if (it.rows > 1) bits |= (uintptr_t)it.src_t_stride_bytes;
+    }
+    GatherItemDev& o = out[k];
+    o.src = (const char*)it.src;
+    o.dst = (char*)it.dst;
+    o.rows = it.rows;
+    o.row_bytes = it.row_bytes;
+    o.stride = (long long)it.src_t_stride_bytes;
+    o.width = !(bits & 15) ? 16 : (!(bits & 7) ? 8 : (!(bits & 3) ? 4 : 1));
+  }
+  return ZB_OK;
+}
+
 float inv_total(double total) { return (float)(1.0 / total); }
 
 AdamCoef adam_coefficients(double beta1, double beta2, int step) {
@@ -439,6 +471,33 @@ int zb_adamw_step_host(float* param, const float* grad, float* m, float* v, size
   const float scale = zbl_clip_scale(sqnorms, k, max_grad_norm);
   for (size_t i = 0; i < count - frozen_tail; i++)
     zbl_adamw(&param[i], &m[i], &v[i], grad[i], scale, lr, c.beta1, c.omb1, c.beta2, c.omb2, c.bc1, c.bc2, eps, weight_decay);
+  return ZB_OK;
+}
+
+int zb_minibatch_perm_host(uint64_t seed, uint32_t epoch, int n, int32_t* perm) {
+  if (!perm || n < 1) return fail(ZB_EARG, "zb_minibatch_perm_host: null perm or n = %d", n);
+  for (int i = 0; i < n; i++) perm[i] = (int32_t)zbf_perm_index(seed, epoch, (uint32_t)n, (uint32_t)i);
+  return ZB_OK;
+}
+
+int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                             uint64_t seed, uint32_t epoch) {
+  zb::GatherItemDev it[ZB_GATHER_MAX_ITEMS];
+  if (int rc = zb::check_gather_args("zb_minibatch_gather_host", items, n_items, n, lo, count, it)) return rc;
+  std::vector<uint32_t> p((size_t)count);
+  for (int j = 0; j < count; j++)
+    p[j] = shuffle ? zbf_perm_index(seed, epoch, (uint32_t)n, (uint32_t)(lo + j)) : (uint32_t)(lo + j);
+  for (int k = 0; k < n_items; k++) {
+    const size_t rb = (size_t)it[k].row_bytes;
+    for (int t = 0; t < it[k].rows; t++)
+      for (int j = 0; j < count; j++) {
+        char* d = it[k].dst + ((size_t)t * (size_t)count + (size_t)j) * rb;
+        if (it[k].src)
+          memcpy(d, it[k].src + (size_t)t * (size_t)it[k].stride + (size_t)p[j] * rb, rb);
+        else
+          memset(d, 0, rb);
+      }
+  }
   return ZB_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "zbot.h"
+#include "zbot_ppo.h"
 
 namespace zb {
 
@@ -51,6 +52,18 @@ int check_adamw_args(const char* what, const void* param, const void* grad, cons
 float inv_total(double total);
 struct AdamCoef { float beta1, omb1, beta2, omb2, bc1, bc2; };
 AdamCoef adam_coefficients(double beta1, double beta2, int step);
+
+/* zb_minibatch_gather / _host (include/zbot_ppo.h "Minibatches"): the argument check, which also
+   fills out[n_items] with each item and the access width it moves in: the widest of 16, 8, 4, 1
+   bytes that divides row_bytes, both addresses and, with more than one row, the time stride */
+struct GatherItemDev {
+  const char* src;
+  char* dst;
+  int rows, row_bytes, width;
+  long long stride;
+};
+int check_gather_args(const char* what, const ZbGatherItem* items, int n_items, int n, int lo, int count,
+                      GatherItemDev* out);
 
 }  // namespace zb
 

@@ -215,6 +215,16 @@ hipError_t launch_ppo_loss(LossArgs a, double* sums_out, hipStream_t s);
 hipError_t launch_sqnorm(const float* grad, size_t count, double* partials, double* out, hipStream_t s);
 hipError_t launch_adamw(AdamArgs a, hipStream_t s);
 
+/* the minibatch kernels (zb_minibatch.hip, include/zbot_ppo.h "Minibatches") */
+struct GatherArgs {
+  GatherItemDev it[ZB_GATHER_MAX_ITEMS]; /* zb_host.h: the checked items with their access width */
+  int n_items, n, lo, count, shuffle;
+  uint32_t epoch;
+  uint64_t seed;
+};
+hipError_t launch_minibatch_perm(uint64_t seed, uint32_t epoch, int n, int32_t* perm, hipStream_t s);
+hipError_t launch_minibatch_gather(const GatherArgs& a, hipStream_t s);
+
 }  // namespace zb
 
 #endif

@@ -6,8 +6,9 @@ through ctypes and exposes a ksim-shaped engine/task interface over PyTorch
 device tensors.
 
 Submodules that need torch are imported on demand: `policy` (the GRU actor /
-critic and PolicyRollout), `ppo` (GAE, value targets, advantages) and
-`learner` (gradients through both networks, the PPO loss and update).
+critic and PolicyRollout), `ppo` (GAE, value targets, advantages, minibatch
+gather), `learner` (gradients through both networks, the PPO loss and update)
+and `train` (the Trainer that joins them into the training iteration).
 """
 
 from . import cstructs

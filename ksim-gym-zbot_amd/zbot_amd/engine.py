@@ -99,6 +99,14 @@ def load_library(path: str | None = None) -> C.CDLL:
     for f in ("zb_ppo_loss", "zb_ppo_loss_host", "zb_grad_sqnorm", "zb_grad_sqnorm_host", "zb_adamw_step",
               "zb_adamw_step_host"):
         getattr(L, f).restype = C.c_int
+    # minibatch permutation and gather (include/zbot_ppo.h "Minibatches") and their host twins
+    L.zb_minibatch_perm.argtypes = [C.c_uint64, C.c_uint32, C.c_int, vp, vp]
+    L.zb_minibatch_perm_host.argtypes = [C.c_uint64, C.c_uint32, C.c_int, vp]
+    gather_args = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
+    L.zb_minibatch_gather.argtypes = gather_args + [vp]
+    L.zb_minibatch_gather_host.argtypes = gather_args
+    for f in ("zb_minibatch_perm", "zb_minibatch_perm_host", "zb_minibatch_gather", "zb_minibatch_gather_host"):
+        getattr(L, f).restype = C.c_int
     # GRU actor / critic (include/zbot_policy.h)
     L.zb_policy_param_count.argtypes = [C.c_int]
     L.zb_policy_param_count.restype = C.c_size_t

@@ -142,17 +142,60 @@ def ppo_loss(log_prob, old_log_prob, advantages, values, old_values, value_targe
     return policy_loss + value_loss_coef * value_loss
 
 
+class _ShuffledMinibatches:
+    """The minibatches of a learner with a shuffle seed: minibatch k of pass `epoch` is positions
+    [k batch, (k + 1) batch) of ppo.minibatch_perm(n, seed, epoch), cut by one ppo.gather_minibatch
+    launch (every array of the minibatch, both carries and the reset rows) into buffers kept per
+    minibatch shape, so a steady-state step allocates nothing for them."""
+
+    KEYS = (("obs_a", "obs_actor"), ("acts", "actions"), ("obs_c", "obs_critic"), ("old_lp", "log_prob"),
+            ("old_v", "value"))
+
+    def __init__(self):
+        self._buf = {}
+
+    def cut(self, torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo, count, seed, epoch) -> dict:
+        from . import ppo  # noqa: PLC0415
+
+        src = {k: rollout[name] for k, name in self.KEYS}
+        src["adv"], src["vt"] = ppo_inputs.advantages_t, ppo_inputs.value_targets_t
+        dev = src["acts"].device
+        key = (T, count, dev) + tuple((tuple(x.shape[2:]), x.dtype) for x in src.values())
+        b = self._buf.get(key)
+        if b is None:
+            b = {k: torch.empty((T, count) + tuple(x.shape[2:]), dtype=x.dtype, device=dev) for k, x in src.items()}
+            b["rs"] = torch.empty(T, count, dtype=torch.uint8, device=dev)
+            b["ca"], b["cc"] = torch.empty_like(actor_carry0[:count]), torch.empty_like(critic_carry0[:count])
+            self._buf[key] = b
+        items = [(x, b[k]) for k, x in src.items()]
+        items += [(actor_carry0[None], b["ca"][None]), (critic_carry0[None], b["cc"][None])]
+        if reset is not None:
+            items.append((reset, b["rs"]))  # uint8: the learners convert once per update()
+        else:  # row 0: no reset; row t: done[t - 1]
+            items.append((None, b["rs"][:1]))
+            if T > 1:
+                items.append((rollout["done"], b["rs"][1:]))
+        ppo.gather_minibatch(items, n, lo, count, shuffle_seed=seed, epoch=epoch)
+        return b
+
+
 class PpoLearner:
     """num_passes x env-axis minibatches of AdamW steps behind a global-norm clip
-    (train.py:1314-1324, 1771-1773)."""
+    (train.py:1314-1324, 1771-1773). shuffle_seed=None: contiguous env slices in env order on every
+    pass; a seed: each pass's minibatches follow a keyed permutation of the envs."""
 
     def __init__(self, learning_rate: float = DEFAULT_LEARNING_RATE, max_grad_norm: float = DEFAULT_MAX_GRAD_NORM,
-                 weight_decay: float = DEFAULT_WEIGHT_DECAY):
+                 weight_decay: float = DEFAULT_WEIGHT_DECAY, shuffle_seed: int | None = None):
         import torch  # noqa: PLC0415
 
         self.torch = torch
         self.learning_rate, self.max_grad_norm, self.weight_decay = learning_rate, max_grad_norm, weight_decay
         self.actor = self.critic = self.opt = None
+        # None: contiguous env slices in env order. A seed: pass `epoch`'s minibatches follow
+        # ppo.minibatch_perm(n, shuffle_seed, epoch), the same law as HipPpoLearner's
+        self.shuffle_seed = shuffle_seed
+        self.epoch = 0                   # passes taken
+        self._mb = _ShuffledMinibatches()
 
     def update(self, rollout: dict, ppo_inputs, actor: TrainablePolicy, critic: TrainablePolicy, actor_carry0,
                critic_carry0, reset=None, num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE,
@@ -165,8 +208,9 @@ class PpoLearner:
         (advantages_t, value_targets_t). actor_carry0 / critic_carry0 [n, 5, 128]: the carries as
         they were before the run. reset [T, n]: the rows the run reset its carries with (row 0:
         the previous run's last done flags or None -> zeros; row t: done[t - 1]).
-        Minibatches are contiguous env slices of `batch_size` in env order (ksim shuffles them
-        with its own RNG [U]). Returns the losses, one per optimizer step."""
+        Minibatches are contiguous env slices of `batch_size` in env order, or with a shuffle_seed
+        the same positions of the pass's keyed permutation (ksim shuffles them with its own RNG
+        [U]). Returns the losses, one per optimizer step."""
         torch = self.torch
         if self.opt is None or actor is not self.actor or critic is not self.critic:
             self.actor, self.critic = actor, critic
@@ -175,6 +219,9 @@ class PpoLearner:
                                          weight_decay=self.weight_decay)
         T = rollout["actions"].shape[0]
         n = rollout["actions"].shape[1]
+        if self.shuffle_seed is not None:
+            return self._update_shuffled(rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes,
+                                         batch_size, loss_kw)
         if reset is None:
             reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
             reset[1:] = rollout["done"][:T - 1]
@@ -196,7 +243,32 @@ class PpoLearner:
                 torch.nn.utils.clip_grad_norm_([self.actor.param, self.critic.param], self.max_grad_norm)
                 self.opt.step()
                 losses.append(loss.detach())
+        self.epoch += num_passes
         # the handles serve the next rollout with the updated weights
+        self.actor.sync()
+        self.critic.sync()
+        return losses
+
+    def _update_shuffled(self, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes, batch_size,
+                         loss_kw) -> list:
+        """update() over the keyed permutation's minibatches: the same steps on gathered buffers."""
+        torch = self.torch
+        if reset is not None and reset.dtype != torch.uint8:
+            reset = reset.to(torch.uint8)
+        losses = []
+        for _ in range(num_passes):
+            for lo in range(0, n, batch_size):
+                b = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo,
+                                 min(n, lo + batch_size) - lo, self.shuffle_seed, self.epoch)
+                lp = self.actor.log_prob(b["obs_a"], b["acts"], b["ca"], b["rs"])
+                v = self.critic.value(b["obs_c"], b["cc"], b["rs"])
+                loss = ppo_loss(lp, b["old_lp"], b["adv"], v, b["old_v"], b["vt"], **loss_kw)
+                self.opt.zero_grad(set_to_none=True)
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_([self.actor.param, self.critic.param], self.max_grad_norm)
+                self.opt.step()
+                losses.append(loss.detach())
+            self.epoch += 1
         self.actor.sync()
         self.critic.sync()
         return losses
@@ -212,16 +284,20 @@ class HipPpoLearner:
     up to date at the end of update()).
 
     The learner owns, per network, the flat parameters and AdamW's m and v (float32 device tensors,
-    natural layout) and the step count; state_dict() / load_state_dict() carry them."""
+    natural layout), the step count and the pass count `epoch`; state_dict() / load_state_dict()
+    carry them. shuffle_seed: as PpoLearner's (the same permutation, so the two stay comparable)."""
 
     def __init__(self, learning_rate: float = DEFAULT_LEARNING_RATE, max_grad_norm: float = DEFAULT_MAX_GRAD_NORM,
-                 weight_decay: float = DEFAULT_WEIGHT_DECAY):
+                 weight_decay: float = DEFAULT_WEIGHT_DECAY, shuffle_seed: int | None = None):
         import torch  # noqa: PLC0415
 
         self.torch = torch
         self.learning_rate, self.max_grad_norm, self.weight_decay = learning_rate, max_grad_norm, weight_decay
+        self.shuffle_seed = shuffle_seed  # None: env slices in env order; a seed: PpoLearner's keyed permutation
+        self._mb = _ShuffledMinibatches()
         self.actor = self.critic = None  # the GruPolicy handles the state below belongs to
         self.step = 0                    # optimizer steps taken
+        self.epoch = 0                   # passes taken: the permutation's second key
         self.state = None                # {"actor": {"params", "m", "v"}, "critic": {...}}
         self._loaded = False             # state came from load_state_dict: the next update pushes it to its handles
         self._buf = {}
@@ -244,7 +320,7 @@ class HipPpoLearner:
                 h.set_params(st["params"])
             self._loaded = False
         elif self.state is None or actor is not self.actor or critic is not self.critic:
-            self.state, self.step = {}, 0
+            self.state, self.step, self.epoch = {}, 0, 0
             for net, h in (("actor", actor), ("critic", critic)):
                 p = h.params_tensor()
                 self.state[net] = dict(params=p, m=torch.zeros_like(p), v=torch.zeros_like(p))
@@ -263,7 +339,8 @@ class HipPpoLearner:
 
     def update(self, rollout: dict, ppo_inputs, actor, critic, actor_carry0, critic_carry0, reset=None,
                num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, **loss_kw) -> list:
-        """One PPO update, as PpoLearner.update (same arguments, same minibatches in the same order).
+        """One PPO update, as PpoLearner.update (same arguments, same minibatches in the same order,
+        shuffled by the same permutation when both have the same shuffle_seed).
         Returns one float64 device tensor [6] per optimizer step: zb_ppo_loss's four sums (sum S,
         sum Vt, sum clipped, sum kl), then the row count and value_loss_coef the step used; loss(sums)
         forms the scalar loss from it. Nothing is synchronized."""
@@ -276,9 +353,12 @@ class HipPpoLearner:
                                         self._buf["actor"], self._buf["critic"], self._buf["sq"])
         T = rollout["actions"].shape[0]
         n = rollout["actions"].shape[1]
-        if reset is None:
+        shuffled = self.shuffle_seed is not None
+        if reset is None and not shuffled:
             reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
             reset[1:] = rollout["done"][:T - 1]
+        if shuffled and reset is not None and reset.dtype != torch.uint8:
+            reset = reset.to(torch.uint8)
         coef = float(loss_kw.get("value_loss_coef", DEFAULT_VALUE_LOSS_COEF))
         out = []
         for _ in range(num_passes):
@@ -288,15 +368,22 @@ class HipPpoLearner:
                 def cut(x):
                     return x[:T, lo:hi].contiguous()
 
-                obs_a, acts, obs_c, rs = cut(rollout["obs_actor"]), cut(rollout["actions"]), cut(rollout["obs_critic"]), cut(reset)
-                ca, cc = actor_carry0[lo:hi].contiguous(), critic_carry0[lo:hi].contiguous()
+                if shuffled:
+                    mb = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo, hi - lo,
+                                      self.shuffle_seed, self.epoch)
+                    obs_a, acts, obs_c, rs, ca, cc = mb["obs_a"], mb["acts"], mb["obs_c"], mb["rs"], mb["ca"], mb["cc"]
+                    old_lp, adv, old_v, vt = mb["old_lp"], mb["adv"], mb["old_v"], mb["vt"]
+                else:
+                    obs_a, acts, obs_c, rs = cut(rollout["obs_actor"]), cut(rollout["actions"]), cut(rollout["obs_critic"]), cut(reset)
+                    ca, cc = actor_carry0[lo:hi].contiguous(), critic_carry0[lo:hi].contiguous()
                 lp, scr_a = act.actor_train(obs_a, acts, ca, rs)
                 v, scr_c = cri.critic_train(obs_c, cc, rs)
                 sums = torch.empty(6, dtype=torch.float64, device=lp.device)
                 sums[4], sums[5] = float(T * (hi - lo)), coef
-                d_lp, d_v, _ = ppo.ppo_loss_grad(lp, cut(rollout["log_prob"]), cut(ppo_inputs.advantages_t), v,
-                                                 cut(rollout["value"]), cut(ppo_inputs.value_targets_t), sums=sums,
-                                                 **loss_kw)
+                if not shuffled:
+                    old_lp, adv, old_v, vt = (cut(rollout["log_prob"]), cut(ppo_inputs.advantages_t),
+                                              cut(rollout["value"]), cut(ppo_inputs.value_targets_t))
+                d_lp, d_v, _ = ppo.ppo_loss_grad(lp, old_lp, adv, v, old_v, vt, sums=sums, **loss_kw)
                 # the critic first: its saved activations were written last, so more of them are still in
                 # the cache (autograd runs PpoLearner's backward passes in this order too)
                 cri.critic_backward(obs_c, cc, rs, d_v, scr_c, grad=bc["grad"])
@@ -310,6 +397,7 @@ class HipPpoLearner:
                 act.set_params(sa["params"])
                 cri.set_params(sc["params"])
                 out.append(sums)
+            self.epoch += 1
         for w in wrappers:  # a TrainablePolicy's own copy follows its handle
             with torch.no_grad():
                 w.param.copy_(self.state["actor" if w.policy.kind == ACTOR else "critic"]["params"])
@@ -323,10 +411,10 @@ class HipPpoLearner:
         return -sums[0] / sums[4] + sums[5] * 0.5 * sums[1] / sums[4]
 
     def state_dict(self) -> dict:
-        """{"step", "actor": {"params", "m", "v"}, "critic": {...}} (copies)."""
+        """{"step", "epoch", "actor": {"params", "m", "v"}, "critic": {...}} (copies)."""
         if self.state is None:
             raise ZbError("HipPpoLearner.state_dict(): no state yet (no update() and no load_state_dict())")
-        return dict(step=self.step, **{net: {k: t.clone() for k, t in self.state[net].items()}
+        return dict(step=self.step, epoch=self.epoch, **{net: {k: t.clone() for k, t in self.state[net].items()}
                                        for net in ("actor", "critic")})
 
     def load_state_dict(self, sd: dict) -> None:
@@ -334,5 +422,6 @@ class HipPpoLearner:
         handles it is given and continues the step count."""
         self.state = {net: {k: sd[net][k].clone() for k in ("params", "m", "v")} for net in ("actor", "critic")}
         self.step = int(sd["step"])
+        self.epoch = int(sd.get("epoch", 0))  # a state dict from before the shuffle has none
         self.actor = self.critic = None
         self._loaded = True

@@ -282,6 +282,127 @@ def adamw_step(param, grad, m, v, sqnorms, step: int, lr: float, max_grad_norm: 
                                         C.c_float(weight_decay), int(step), _stream(torch, dev)))
 
 
+# ---- minibatches: the keyed permutation and the fused gather (include/zbot_ppo.h "Minibatches") ----
+GATHER_MAX_ITEMS = 16  # ZB_GATHER_MAX_ITEMS
+
+
+class ZbGatherItem(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("row_bytes", C.c_int32),
+                ("src_t_stride_bytes", C.c_int64)]
+
+
+def _perm_args(n, seed, epoch):
+    n, seed, epoch = int(n), int(seed), int(epoch)
+    if n < 1 or not 0 <= seed < 1 << 64 or not 0 <= epoch < 1 << 32:
+        raise ZbError(f"minibatch permutation: n >= 1, a 64-bit seed and a 32-bit epoch, got {n}, {seed}, {epoch}")
+    return n, seed, epoch
+
+
+def minibatch_perm(n: int, seed: int, epoch: int = 0, device=None):
+    """zb_minibatch_perm: perm[i] = zbf_perm_index(seed, epoch, n, i), an int32 device tensor [n]: the
+    order in which pass `epoch` of a learner with shuffle_seed=seed visits the n envs."""
+    import torch  # noqa: PLC0415
+
+    n, seed, epoch = _perm_args(n, seed, epoch)
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ZbError("ppo.minibatch_perm runs on the GPU (libzbot_hip.so); minibatch_perm_host is the CPU twin")
+    out = torch.empty(n, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _check(load_library().zb_minibatch_perm(seed, epoch, n, out.data_ptr(), _stream(torch, dev)))
+    return out
+
+
+def minibatch_perm_host(n: int, seed: int, epoch: int = 0):
+    """zb_minibatch_perm_host: the same permutation on the CPU, an int32 numpy array [n]."""
+    import numpy as np  # noqa: PLC0415
+
+    n, seed, epoch = _perm_args(n, seed, epoch)
+    out = np.empty(n, np.int32)
+    _check(load_library().zb_minibatch_perm_host(seed, epoch, n, out.ctypes.data))
+    return out
+
+
+def _gather_table(items, n, count, describe):
+    """The ZbGatherItem array of `items`, pairs (src, dst): dst [rows, count, ...] dense, src
+    [>= rows, n, ...] with the same trailing shape and dtype, dense below its first axis (any stride
+    along it), or None for zeros. `describe(x)` -> (address, shape, strides in bytes, itemsize, dtype)."""
+    items = list(items)
+    if not 1 <= len(items) <= GATHER_MAX_ITEMS:
+        raise ZbError(f"gather_minibatch takes 1 to {GATHER_MAX_ITEMS} items, got {len(items)}")
+    table = (ZbGatherItem * len(items))()
+    for k, (src, dst) in enumerate(items):
+        dp, dshape, dstr, isz, ddt = describe(dst)
+        if len(dshape) < 2 or dshape[1] != count or dshape[0] < 1:
+            raise ZbError(f"item {k}: dst must be [rows, {count}, ...], got {list(dshape)}")
+        dense = [isz] * len(dshape)
+        for a in range(len(dshape) - 2, -1, -1):
+            dense[a] = dense[a + 1] * dshape[a + 1]
+        if any(st != dn for st, dn, sz in zip(dstr, dense, dshape) if sz != 1):  # a size-1 axis has no stride
+            raise ZbError(f"item {k}: dst must be contiguous")
+        rows, row_bytes = dshape[0], dense[1]
+        sp, stride = None, 0
+        if src is not None:
+            sp, sshape, sstr, _, sdt = describe(src)
+            if (sdt != ddt or len(sshape) != len(dshape) or sshape[0] < rows or sshape[1] != n
+                    or tuple(sshape[2:]) != tuple(dshape[2:])):
+                raise ZbError(f"item {k}: src {list(sshape)} {sdt} does not feed dst {list(dshape)} {ddt} over "
+                              f"{n} envs")
+            if any(st != dn for st, dn, sz in zip(sstr[1:], dense[1:], sshape[1:]) if sz != 1) or sstr[0] < 0:
+                raise ZbError(f"item {k}: src must be dense below its first axis")
+            stride = sstr[0] if rows > 1 else 0
+        table[k] = ZbGatherItem(sp, dp, rows, row_bytes, stride)
+    return table
+
+
+def gather_minibatch(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0) -> None:
+    """zb_minibatch_gather: one launch that cuts every array of a minibatch. For each pair (src, dst)
+    of `items` (device tensors; at most 16) and every t < rows, j < count:
+    dst[t, j] = src[t, p(lo + j)], p = minibatch_perm(n, shuffle_seed, epoch), or the identity (a
+    slice) when shuffle_seed is None. dst is [rows, count, ...], contiguous; src is [>= rows, n, ...]
+    of the same dtype and trailing shape, dense below its first axis (the first T rows of a [T + 1]
+    buffer, or any stride along time), or None, which fills dst with zeros. A per-env array such as
+    a carry goes in as src[None], dst[None]. Asynchronous on the current stream; allocates nothing
+    on the device."""
+    import torch  # noqa: PLC0415
+
+    items = list(items)
+    dev = items[0][1].device if items else None
+    if dev is None or dev.type != "cuda":
+        raise ZbError("ppo.gather_minibatch runs on the GPU (libzbot_hip.so); gather_minibatch_host is the CPU twin")
+
+    def describe(x):
+        if not isinstance(x, torch.Tensor) or x.device != dev:
+            raise ZbError(f"gather_minibatch: every tensor must live on {dev}")
+        isz = x.element_size()
+        return x.data_ptr(), tuple(x.shape), tuple(s * isz for s in x.stride()), isz, x.dtype
+
+    n, seed, epoch = _perm_args(n, 0 if shuffle_seed is None else shuffle_seed, epoch)
+    table = _gather_table(items, n, int(count), describe)
+    with torch.cuda.device(dev):
+        _check(load_library().zb_minibatch_gather(table, len(table), n, int(lo), int(count),
+                                                  0 if shuffle_seed is None else 1, seed, epoch, _stream(torch, dev)))
+
+
+def gather_minibatch_host(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0) -> None:
+    """zb_minibatch_gather_host: gather_minibatch on numpy arrays (or CPU tensors), in place on each dst."""
+    import numpy as np  # noqa: PLC0415
+
+    def describe(x):
+        if hasattr(x, "detach"):
+            if x.device.type != "cpu":
+                raise ZbError("gather_minibatch_host takes CPU tensors or numpy arrays")
+            x = x.detach().numpy()
+        if not isinstance(x, np.ndarray):
+            raise ZbError("gather_minibatch_host takes CPU tensors or numpy arrays")
+        return x.ctypes.data, x.shape, x.strides, x.itemsize, x.dtype
+
+    n, seed, epoch = _perm_args(n, 0 if shuffle_seed is None else shuffle_seed, epoch)
+    table = _gather_table(list(items), n, int(count), describe)
+    _check(load_library().zb_minibatch_gather_host(table, len(table), n, int(lo), int(count),
+                                                   0 if shuffle_seed is None else 1, seed, epoch))
+
+
 def _host(a, dtype, name, writable=False):
     """A contiguous numpy view of a CPU tensor or numpy array (no copy: the twins write in place)."""
     import numpy as np  # noqa: PLC0415

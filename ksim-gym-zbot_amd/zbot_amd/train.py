@@ -1,0 +1,163 @@
+"""The training iteration of the reference's ZbotWalkingTask.launch (train.py:1766-1788), joined
+from the library's blocks: rollout with the GRU actor and the in-loop critic, PPO inputs, the PPO
+update in HIP, the episode-length curriculum.
+
+    tr = Trainer(engine, actor, critic, rollout_steps=200, num_passes=4, batch_size=128,
+                 seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, **learner_kw)
+    m = tr.step()            # one iteration; returns metrics
+    sd = tr.state_dict(); tr.load_state_dict(sd)
+
+`engine` is a HipEngine or an EnvGroups, `actor` / `critic` are GruPolicy handles; the remaining
+keyword arguments go to HipPpoLearner (learning_rate, max_grad_norm, weight_decay). Saving to a file
+is the caller's torch.save(tr.state_dict(), path); file formats, logging, the command line and the
+viewer are out of scope.
+
+One step(), in order:
+  1. open the statistics window: engine.get_stats(clear=True);
+  2. snapshot both carries (the learner's carry0 arguments: the carries before the run);
+  3. PolicyRollout.run(T, record_critic=True, critic=..., critic_carry=...) at the current level;
+  4. ppo.compute_ppo_inputs(value, reward, done, success, bootstrap=value_next);
+  5. HipPpoLearner.update(...), `reset` row 0 = the previous iteration's last done flags (none in
+     the first), row t = done[t - 1];
+  6. curriculum.rollout_episode_length and curriculum.update: the iteration's one host
+     synchronisation is that float;
+  7. the new level goes to the next rollout.
+"""
+
+from __future__ import annotations
+
+from . import ppo
+from .curriculum import CurriculumState, EpisodeLengthCurriculum, rollout_episode_length
+from .engine import ZbError
+from .learner import DEFAULT_BATCH_SIZE, DEFAULT_NUM_PASSES, HipPpoLearner
+from .policy import ACTOR, GruPolicy, PolicyRollout
+
+DEFAULT_ROLLOUT_STEPS = 200  # rollout_length_seconds 4.0 / ctrl_dt 0.02 (train.py:1775, 1783)
+
+
+class Trainer:
+    """One training process on one GPU: owns the PolicyRollout, the critic's carry, the
+    HipPpoLearner and the curriculum state. The seed keys the actor's action samples and, with
+    shuffle, the minibatch permutation (shuffle=False: env slices in env order). Everything runs
+    on the current stream; two Trainers built from the same seeds, weights and engine seed produce
+    the same bits, and so does one continued from state_dict() in a fresh process."""
+
+    def __init__(self, engine, actor: GruPolicy, critic: GruPolicy, rollout_steps: int = DEFAULT_ROLLOUT_STEPS,
+                 num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, seed: int = 0,
+                 shuffle: bool = True, curriculum: EpisodeLengthCurriculum | None = None, ctrl_dt: float = 0.02,
+                 **learner_kw):
+        if actor.kind != ACTOR or critic.kind == ACTOR:
+            raise ZbError("Trainer(engine, actor, critic): an actor and a critic handle, in this order")
+        if rollout_steps < 1 or num_passes < 1 or batch_size < 1:
+            raise ZbError("rollout_steps, num_passes and batch_size must be >= 1")
+        self.torch = actor.torch
+        self.eng, self.actor, self.critic = engine, actor, critic
+        self.T, self.num_passes, self.batch_size = int(rollout_steps), int(num_passes), int(batch_size)
+        self.seed, self.shuffle, self.ctrl_dt = int(seed), bool(shuffle), float(ctrl_dt)
+        self.curriculum = EpisodeLengthCurriculum() if curriculum is None else curriculum
+        self.cur_state = self.curriculum.initial_state()
+        self.rollout = PolicyRollout(engine, actor, seed=self.seed, curriculum=self.cur_state.level)
+        self.critic_carry = critic.initial_carry(engine.n)
+        self.learner = HipPpoLearner(shuffle_seed=self.seed if self.shuffle else None, **learner_kw)
+        self.iteration = 0
+        self.last_rollout = None  # the last step()'s rollout dict and PPO inputs, for inspection
+        self.last_inputs = None
+        self.timing = None        # {"rollout": (start, end), ...} torch.cuda.Event pairs: step() records them
+
+    @property
+    def level(self) -> float:
+        return self.cur_state.level
+
+    def _mark(self, name: str, end: bool) -> None:
+        if self.timing is not None:
+            self.timing[name][1 if end else 0].record()
+
+    def step(self) -> dict:
+        """One training iteration. Returns {"iteration", "level" (the level the rollout ran at),
+        "episode_length" (seconds, a float), "reward" (mean per env-step), "loss", "clip_fraction",
+        "approx_kl" ([optimizer steps] each), "sums" (HipPpoLearner.update's list)}; the tensors are
+        on the device and nothing but the episode length is synchronised."""
+        torch = self.torch
+        ro, T = self.rollout, self.T
+        self.eng.get_stats(clear=True)
+        if ro.obs is None:
+            ro.reset()
+        carry0, ccarry0 = ro.carry.clone(), self.critic_carry.clone()
+        prev_done = ro.done
+        level = self.cur_state.level
+        ro.curriculum = level
+        self._mark("rollout", False)
+        out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry)
+        self._mark("rollout", True)
+        self._mark("ppo_inputs", False)
+        inputs = ppo.compute_ppo_inputs(out["value"], out["reward"], out["done"], out["success"],
+                                        bootstrap=out["value_next"])
+        self._mark("ppo_inputs", True)
+        reset = None
+        if prev_done is not None:
+            reset = torch.cat([prev_done[None], out["done"][:T - 1]])
+        self._mark("update", False)
+        sums = self.learner.update(out, inputs, self.actor, self.critic, carry0, ccarry0, reset=reset,
+                                   num_passes=self.num_passes, batch_size=self.batch_size)
+        self._mark("update", True)
+        length = rollout_episode_length(self.eng.get_stats(), self.eng.get_state(), out["done"][T - 1], self.ctrl_dt)
+        self.cur_state = self.curriculum.update(self.cur_state, length)
+        self.iteration += 1
+        self.last_rollout, self.last_inputs = out, inputs
+        s = torch.stack(sums)
+        return dict(iteration=self.iteration, level=level, episode_length=length, reward=out["reward"].mean(),
+                    loss=-s[:, 0] / s[:, 4] + s[:, 5] * 0.5 * s[:, 1] / s[:, 4], clip_fraction=s[:, 2] / s[:, 4],
+                    approx_kl=s[:, 3] / s[:, 4], sums=sums)
+
+    def state_dict(self) -> dict:
+        """Everything a fresh process needs to continue with the same bits (copies): the engine's
+        state and randomisation rows, the rollout's current observations, done flags, actor carry
+        and step count, the critic carry, both networks' weights, the learner's state (weights, m,
+        v, step, epoch; None before the first step), the curriculum state, the iteration count and
+        the seeds. The engine
+        and the policy handles themselves are the caller's to create: the engine with the same
+        model, config, env count and seed (checked on load), the handles from any weights."""
+        ro = self.rollout
+        if ro.obs is None:
+            ro.reset()
+        c = lambda t: None if t is None else t.clone()  # noqa: E731
+        return dict(
+            engine=dict(state=self.eng.get_state(), rand=self.eng.get_rand(), seed=int(self.eng.seed), n=int(self.eng.n)),
+            rollout=dict(obs=c(ro.obs), obs_c=c(ro.obs_c), done=c(ro.done), carry=ro.carry.clone(),
+                         step_count=int(ro.step_count)),
+            critic_carry=self.critic_carry.clone(),
+            params=dict(actor=self.actor.params_tensor(), critic=self.critic.params_tensor()),
+            learner=None if self.learner.state is None else self.learner.state_dict(),
+            curriculum=dict(level=float(self.cur_state.level), steps=int(self.cur_state.steps)),
+            iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle)
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Restore state_dict()'s result into this Trainer's engine, handles and learner."""
+        torch = self.torch
+        dev = self.eng.device
+        e = sd["engine"]
+        if int(e["n"]) != self.eng.n or int(e["seed"]) != int(self.eng.seed):
+            raise ZbError(f"the state is of {e['n']} envs with engine seed {e['seed']}; this engine has {self.eng.n}, "
+                          f"seed {self.eng.seed}")
+        if int(sd["seed"]) != self.seed or bool(sd["shuffle"]) != self.shuffle:
+            raise ZbError(f"the state was trained with seed={sd['seed']}, shuffle={sd['shuffle']}")
+        self.eng.set_state(e["state"])
+        self.eng.set_rand(e["rand"])
+        ro, r = self.rollout, sd["rollout"]
+        to = lambda t: None if t is None else t.to(dev).clone()  # noqa: E731
+        ro.obs, ro.obs_c, ro.done = to(r["obs"]), to(r["obs_c"]), to(r["done"])
+        ro.carry.copy_(r["carry"])
+        ro.step_count = int(r["step_count"])
+        self.critic_carry.copy_(sd["critic_carry"])
+        self.learner = HipPpoLearner(learning_rate=self.learner.learning_rate, max_grad_norm=self.learner.max_grad_norm,
+                                     weight_decay=self.learner.weight_decay,
+                                     shuffle_seed=self.seed if self.shuffle else None)
+        # the next rollout comes before the next update: the handles need the weights now
+        self.actor.set_params(sd["params"]["actor"].to(dev, dtype=torch.float32))
+        self.critic.set_params(sd["params"]["critic"].to(dev, dtype=torch.float32))
+        if sd["learner"] is not None:
+            self.learner.load_state_dict(sd["learner"])
+        self.cur_state = CurriculumState(level=float(sd["curriculum"]["level"]), steps=int(sd["curriculum"]["steps"]))
+        ro.curriculum = self.cur_state.level
+        self.iteration = int(sd["iteration"])
+        self.last_rollout = self.last_inputs = None

@@ -31,5 +31,5 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$CSRC -fno-s
 wait -n
 wait -n
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libeng_$NAME.so" "$OUT/eng_$NAME.o" "$OUT/eng_${NAME}_b.o" \
-  "$CSRC/build/zb_capi.o" "$CSRC/build/zb_ppo.o" "$CSRC/build/zb_policy.o" "$CSRC/build/zb_policy_train.o" "$CSRC/build/zb_learner.o" "$CSRC/build/zb_host.o"
+  "$CSRC/build/zb_capi.o" "$CSRC/build/zb_ppo.o" "$CSRC/build/zb_policy.o" "$CSRC/build/zb_policy_train.o" "$CSRC/build/zb_learner.o" "$CSRC/build/zb_minibatch.o" "$CSRC/build/zb_host.o"
 echo "built $OUT/libeng_$NAME.so"
