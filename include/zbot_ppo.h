@@ -92,6 +92,8 @@ int zb_adv_normalize(const float* gae, float* advantages, long long count, const
  *   zb_ppo_loss                                          -> d_log_prob, d_value, sums
  *   zb_policy_actor_backward / zb_policy_critic_backward -> one flat gradient per network
  *   zb_grad_sqnorm (one per network)                     -> sqnorms[k]
+ *     (several ranks: an all-gather of the gradient and zb_grad_combine instead, which sums the
+ *      ranks' gradients and returns the sum's squared norm)
  *   zb_adamw_step  (one per network, the same sqnorms)   params, m, v in place
  *   zb_policy_set_params
  *
@@ -154,6 +156,25 @@ size_t zb_sqnorm_partials_words(size_t count);
  */
 int zb_grad_sqnorm(const float* grad, size_t count, double* partials, double* out, void* stream);
 int zb_grad_sqnorm_host(const float* grad, size_t count, double* out);
+
+/*
+ * The gradient sum over ranks, by the tree above instead of a collective's own order: `parts` is
+ * [world][count] fp32, densely packed (the destination of an all-gather of every rank's flat
+ * gradient, row r from rank r). For every i < count
+ *   grad[i] = (float)(tree over the world leaves (double)parts[r][i], r ascending)
+ * i.e. the leaves zero-padded to a power of two, combined in fp64 by the balanced pairwise tree,
+ * the root added to +0.0 and rounded to fp32 once. Every rank that holds the same `parts` gets the
+ * same bits, whatever ring or tree moved them.
+ *   partials   [zb_sqnorm_partials_words(count)] fp64 scratch
+ *   sq_out     [1] fp64: bit for bit what zb_grad_sqnorm returns on the `grad` just written (the
+ *              same leaves and tree; the combined gradient is read once, not twice)
+ * 1 <= world <= ZB_COMBINE_MAX_WORLD, 1 <= count <= 2^32; grad must not overlap parts. Rows are read
+ * in 16-byte accesses when parts, grad and every row start are 16-byte aligned, else in 4-byte ones.
+ */
+#define ZB_COMBINE_MAX_WORLD 64
+int zb_grad_combine(const float* parts, int world, size_t count, float* grad, double* partials, double* sq_out,
+                    void* stream);
+int zb_grad_combine_host(const float* parts, int world, size_t count, float* grad, double* sq_out);
 
 /*
  * One AdamW step behind the global-norm clip, in place on param, m, v [count] (fp32):

@@ -480,6 +480,16 @@ int zb_grad_sqnorm(const float* grad, size_t count, double* partials, double* ou
   return ZB_OK;
 }
 
+int zb_grad_combine(const float* parts, int world, size_t count, float* grad, double* partials, double* sq_out,
+                    void* stream) {
+  if (int rc = zb::check_combine_args("zb_grad_combine", parts, world, count, grad, sq_out)) return rc;
+  if (!partials) return fail(ZB_EARG, "zb_grad_combine: null partials");
+  hipError_t e = zb::launch_grad_combine(parts, world, count, grad, partials, sq_out,
+                                         zb::combine_width(parts, world, count, grad) == 16, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_grad_combine launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
 int zb_adamw_step(float* param, const float* grad, float* m, float* v, size_t count, size_t frozen_tail,
                   const double* sqnorms, int k, float max_grad_norm, float lr, double beta1, double beta2, float eps,
                   float weight_decay, int step, void* stream) {

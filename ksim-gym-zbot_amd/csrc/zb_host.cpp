@@ -351,6 +351,25 @@ int check_sqnorm_args(const char* what, const void* grad, size_t count, const vo
   return ZB_OK;
 }
 
+int check_combine_args(const char* what, const float* parts, int world, size_t count, const float* grad,
+                       const void* sq_out) {
+  if (!parts || !grad || !sq_out) return fail(ZB_EARG, "%s: null pointer", what);
+  if (world < 1 || world > ZB_COMBINE_MAX_WORLD)
+    return fail(ZB_EARG, "%s: world = %d (1 to %d)", what, world, ZB_COMBINE_MAX_WORLD);
+  if (count < 1 || (unsigned long long)count > (1ull << 32))
+    return fail(ZB_EARG, "%s: count = %zu (1 to 2^32)", what, count);
+  const uintptr_t p0 = (uintptr_t)parts, p1 = p0 + (uintptr_t)world * count * sizeof(float);
+  const uintptr_t g0 = (uintptr_t)grad, g1 = g0 + count * sizeof(float);
+  if (g0 < p1 && p0 < g1) return fail(ZB_EARG, "%s: grad overlaps parts", what);
+  return ZB_OK;
+}
+
+int combine_width(const float* parts, int world, size_t count, const float* grad) {
+  uintptr_t bits = (uintptr_t)parts | (uintptr_t)grad;
+  if (world > 1) bits |= (uintptr_t)(count * sizeof(float)); /* the stride between row starts */
+  return !(bits & 15) ? 16 : 4;
+}
+
 int check_adamw_args(const char* what, const void* param, const void* grad, const void* m, const void* v,
                      size_t count, size_t frozen_tail, const void* sqnorms, int k, float max_grad_norm, float lr,
                      double beta1, double beta2, float eps, float weight_decay, int step) {
@@ -458,6 +477,14 @@ int zb_ppo_loss_host(const float* log_prob, const float* old_log_prob, const flo
 int zb_grad_sqnorm_host(const float* grad, size_t count, double* out) {
   if (int rc = zb::check_sqnorm_args("zb_grad_sqnorm_host", grad, count, out)) return rc;
   out[0] = zb::tree_root([&](size_t i) { const double g = (double)grad[i]; return g * g; }, count);
+  return ZB_OK;
+}
+
+int zb_grad_combine_host(const float* parts, int world, size_t count, float* grad, double* sq_out) {
+  if (int rc = zb::check_combine_args("zb_grad_combine_host", parts, world, count, grad, sq_out)) return rc;
+  for (size_t i = 0; i < count; i++)
+    grad[i] = (float)zb::tree_root([&](size_t r) { return (double)parts[r * count + i]; }, (size_t)world);
+  sq_out[0] = zb::tree_root([&](size_t i) { const double g = (double)grad[i]; return g * g; }, count);
   return ZB_OK;
 }
 

@@ -44,6 +44,11 @@ void build_topology(const ZbModel* m, int32_t t[TP_NF][TOPO_LANES]);
 int check_loss_args(const char* what, const void* const* ptrs, int nptrs, int T, int n, double total,
                     float clip_param, float log_clip_value);
 int check_sqnorm_args(const char* what, const void* grad, size_t count, const void* out);
+/* zb_grad_combine / _host: the check, and the access width the kernel reads rows in: 16 bytes when
+   parts, grad and (with more than one row) the row stride count * 4 are multiples of 16, else 4 */
+int check_combine_args(const char* what, const float* parts, int world, size_t count, const float* grad,
+                       const void* sq_out);
+int combine_width(const float* parts, int world, size_t count, const float* grad);
 int check_adamw_args(const char* what, const void* param, const void* grad, const void* m, const void* v,
                      size_t count, size_t frozen_tail, const void* sqnorms, int k, float max_grad_norm, float lr,
                      double beta1, double beta2, float eps, float weight_decay, int step);

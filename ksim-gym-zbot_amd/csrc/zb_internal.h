@@ -213,6 +213,8 @@ struct AdamArgs {
 };
 hipError_t launch_ppo_loss(LossArgs a, double* sums_out, hipStream_t s);
 hipError_t launch_sqnorm(const float* grad, size_t count, double* partials, double* out, hipStream_t s);
+hipError_t launch_grad_combine(const float* parts, int world, size_t count, float* grad, double* partials,
+                               double* sq_out, bool vec, hipStream_t s);
 hipError_t launch_adamw(AdamArgs a, hipStream_t s);
 
 /* the minibatch kernels (zb_minibatch.hip, include/zbot_ppo.h "Minibatches") */

@@ -17,6 +17,10 @@
  *                    partials[chunk].
  *   tree_finish      one workgroup: the pairwise tree over the partials (groups of 1024, then
  *                    the group roots), zero-padded; root + 0.0 to the output.
+ *   grad_combine_kernel  the gradient sum over ranks: sqnorm_kernel's chunks and first stage, with
+ *                    each element first formed as the fp64 pairwise tree over the ranks' rows (in rank
+ *                    order, a recursion with one accumulator per level) and stored as fp32; then
+ *                    tree_finish, so the squared norm costs no second read of the gradient.
  *   adamw_kernel     grid-stride float4 stream over the live elements (count - frozen_tail), a
  *                    scalar tail; every thread forms the clip factor from the k squared norms.
  *
@@ -172,6 +176,132 @@ __global__ __launch_bounds__(256) void sqnorm_kernel(const float* g, size_t coun
   }
 }
 
+/* ---- zb_grad_combine: the rank tree of every element, and the squared norm of the result ---- */
+
+struct Col4 {
+  double v[4];
+};
+
+/* Elements e .. e + 3 of the row that `row` points into (at element e) as fp64 leaves; `row` then
+   moves on to the next rank's row (the tree visits the rows in rank order, each once).
+   MODE 2: one 16-byte load; 1: four 4-byte loads; 0: a chunk with a ragged end, where elements
+   past `count` are +0.0 leaves (never stored). */
+template <int MODE>
+__device__ inline Col4 combine_leaf(const float*& row, size_t count, size_t e) {
+  float x[4];
+  if constexpr (MODE == 2) {
+    const float4 t = *reinterpret_cast<const float4*>(row);
+    x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+  } else if constexpr (MODE == 1) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = row[c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = e + c < count ? row[c] : 0.0f;
+  }
+  row += count;
+  Col4 o;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) o.v[c] = (double)x[c];
+  return o;
+}
+
+/* The balanced pairwise tree over rows r0 .. r0 + LEN - 1 (LEN a power of two, r0 < world); rows at or
+   past `world` are the zero padding, and adding +0.0 is exact, so an absent right half is skipped (the
+   sign of an all-zero sum is settled by the caller's root + 0.0). `world` is uniform, so every branch
+   is; the recursion keeps one accumulator per level live: log2(ZB_COMBINE_MAX_WORLD) + 1 = 7 per
+   element, no world-sized array. Four whole rows are loaded together before they are added. */
+template <int MODE, int LEN>
+__device__ inline Col4 rank_tree(const float*& row, size_t count, int world, int r0, size_t e) {
+#pragma clang fp contract(off)
+  if constexpr (LEN == 1) {
+    return combine_leaf<MODE>(row, count, e);
+  } else {
+    if constexpr (LEN == 4) {
+      if (r0 + 4 <= world) {
+        const Col4 a = combine_leaf<MODE>(row, count, e);
+        const Col4 b = combine_leaf<MODE>(row, count, e);
+        const Col4 c = combine_leaf<MODE>(row, count, e);
+        const Col4 d = combine_leaf<MODE>(row, count, e);
+        Col4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const double lo = a.v[k] + b.v[k], hi = c.v[k] + d.v[k];
+          o.v[k] = lo + hi;
+        }
+        return o;
+      }
+    }
+    Col4 a = rank_tree<MODE, LEN / 2>(row, count, world, r0, e);
+    if (r0 + LEN / 2 < world) {
+      const Col4 b = rank_tree<MODE, LEN / 2>(row, count, world, r0 + LEN / 2, e);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) a.v[k] = a.v[k] + b.v[k];
+    }
+    return a;
+  }
+}
+
+/* One chunk: a thread owns the float4s q = j 256 + tid, j < 4, as in sqnorm_kernel; per float4 it
+   streams the rows in rank order through rank_tree, rounds root + 0.0 to fp32 once, stores it, and
+   leaves the square of the rounded value in node[q] exactly as sqnorm_kernel forms it. */
+template <int MODE>
+__device__ inline void combine_chunk(const float* parts, int world, size_t count, size_t base, float* grad,
+                                     double* node) {
+#pragma clang fp contract(off)
+#pragma unroll 1
+  for (int j = 0; j < SQ_NODES / 256; ++j) {
+    const int q = j * 256 + (int)threadIdx.x;
+    const size_t e = base + 4 * (size_t)q;
+    double s = 0.0;
+    if (MODE != 0 || e < count) { /* a float4 wholly past the end is a +0.0 node and touches no memory */
+      const float* row = parts + e; /* this float4 in rank 0's row */
+      /* keeps the tree's ~100 comparisons with `world` beside their branches: hoisted out of this
+         loop, each would hold a scalar register pair across it, more than there are */
+      int w = world;
+      asm volatile("" : "+s"(w));
+      const Col4 t = rank_tree<MODE, ZB_COMBINE_MAX_WORLD>(row, count, w, 0, e);
+      float x[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[c] = (float)(t.v[c] + 0.0);
+      if constexpr (MODE == 2) {
+        *reinterpret_cast<float4*>(grad + e) = make_float4(x[0], x[1], x[2], x[3]);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+          if (MODE == 1 || e + c < count) grad[e + c] = x[c];
+      }
+      const double d0 = (double)x[0], d1 = (double)x[1], d2 = (double)x[2], d3 = (double)x[3];
+      const double q0 = d0 * d0, q1 = d1 * d1, q2 = d2 * d2, q3 = d3 * d3;
+      const double lo = q0 + q1, hi = q2 + q3;
+      s = lo + hi;
+    }
+    node[q] = s;
+  }
+}
+
+/* One workgroup per 4096-element chunk (grid-stride past MAX_BLOCKS). A chunk that lies wholly below
+   `count` moves in 16-byte accesses (vec: parts, grad and the row stride allow it) or 4-byte ones;
+   the last, ragged chunk in guarded 4-byte ones. Then the chunk's tree, the same tree1 over the
+   same nodes as sqnorm_kernel: partials[chunk] is what zb_grad_sqnorm's first stage writes for
+   this grad. */
+__global__ __launch_bounds__(256) void grad_combine_kernel(const float* parts, int world, size_t count, size_t nchunks,
+                                                           float* grad, double* partials, int vec) {
+  __shared__ double node[SQ_NODES];
+  for (size_t ch = blockIdx.x; ch < nchunks; ch += gridDim.x) {
+    const size_t base = ch * SQ_CHUNK;
+    if (base + SQ_CHUNK > count)
+      combine_chunk<0>(parts, world, count, base, grad, node);
+    else if (vec)
+      combine_chunk<2>(parts, world, count, base, grad, node);
+    else
+      combine_chunk<1>(parts, world, count, base, grad, node);
+    tree1<SQ_NODES>(node);
+    if (threadIdx.x == 0) partials[ch] = node[0];
+    __syncthreads(); /* node is rewritten by the next chunk */
+  }
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
 #pragma clang fp contract(off)
   const float scale = zbl_clip_scale(a.sqnorms, a.k, a.max_grad_norm);
@@ -218,6 +348,18 @@ hipError_t launch_sqnorm(const float* grad, size_t count, double* partials, doub
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(tree_finish_kernel, dim3(1), dim3(FTREE), 0, s, partials, (int)nchunks, 1, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_grad_combine(const float* parts, int world, size_t count, float* grad, double* partials,
+                               double* sq_out, bool vec, hipStream_t s) {
+  const size_t nchunks = (count + SQ_CHUNK - 1) / SQ_CHUNK;
+  const int blocks = (int)(nchunks < (size_t)MAX_BLOCKS ? nchunks : (size_t)MAX_BLOCKS);
+  hipLaunchKernelGGL(grad_combine_kernel, dim3(blocks), dim3(256), 0, s, parts, world, count, nchunks, grad, partials,
+                     vec ? 1 : 0);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(tree_finish_kernel, dim3(1), dim3(FTREE), 0, s, partials, (int)nchunks, 1, sq_out);
   return hipGetLastError();
 }
 

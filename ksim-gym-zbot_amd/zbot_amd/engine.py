@@ -96,8 +96,10 @@ def load_library(path: str | None = None) -> C.CDLL:
     adam_args = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_int, fl, fl, C.c_double, C.c_double, fl, fl, C.c_int]
     L.zb_adamw_step.argtypes = adam_args + [vp]
     L.zb_adamw_step_host.argtypes = adam_args
+    L.zb_grad_combine.argtypes = [vp, C.c_int, C.c_size_t, vp, vp, vp, vp]
+    L.zb_grad_combine_host.argtypes = [vp, C.c_int, C.c_size_t, vp, vp]
     for f in ("zb_ppo_loss", "zb_ppo_loss_host", "zb_grad_sqnorm", "zb_grad_sqnorm_host", "zb_adamw_step",
-              "zb_adamw_step_host"):
+              "zb_adamw_step_host", "zb_grad_combine", "zb_grad_combine_host"):
         getattr(L, f).restype = C.c_int
     # minibatch permutation and gather (include/zbot_ppo.h "Minibatches") and their host twins
     L.zb_minibatch_perm.argtypes = [C.c_uint64, C.c_uint32, C.c_int, vp, vp]

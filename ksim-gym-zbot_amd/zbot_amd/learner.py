@@ -24,6 +24,8 @@ PolicyRollout with the updated weights.
 
 from __future__ import annotations
 
+import struct
+
 from .engine import ZbError
 from .policy import ACTOR, JOINTS, GruPolicy
 
@@ -38,6 +40,7 @@ DEFAULT_CLIP_PARAM = 0.2        # [U]
 DEFAULT_VALUE_LOSS_COEF = 0.5   # [U]
 DEFAULT_USE_CLIPPED_VALUE_LOSS = True  # [U]
 DEFAULT_LOG_CLIP_VALUE = 10.0   # [U] bound on the log ratio before exp
+RANK_SEED_STRIDE = 0x9E3779B97F4A7C15  # rank r shuffles with (shuffle_seed + r x this) mod 2^64
 
 
 def _function():
@@ -285,15 +288,33 @@ class HipPpoLearner:
 
     The learner owns, per network, the flat parameters and AdamW's m and v (float32 device tensors,
     natural layout), the step count and the pass count `epoch`; state_dict() / load_state_dict()
-    carry them. shuffle_seed: as PpoLearner's (the same permutation, so the two stay comparable)."""
+    carry them. shuffle_seed: as PpoLearner's (the same permutation, so the two stay comparable).
+
+    group: a torch.distributed process group of W ranks that train one model on W shards of the envs
+    (DESIGN.md §4p); None, or a group of one rank: this process alone, no collective. With W > 1
+    every rank calls update() with its own rollout of the same shape and the global `batch_size`
+    (a multiple of W): minibatch k is positions [k b, (k + 1) b), b = batch_size / W, of each rank's
+    own env order (with a seed: the rank's own permutation, keyed by rank_seed()), the loss means run
+    over the global rows, and per step and network the ranks' gradients are all-gathered
+    (dist.all_gather_rows) and summed in rank order by ppo.grad_combine, which also returns the sum's
+    squared norm. Gradient, norms and so params, m and v are the same bits on every rank without a
+    broadcast; the ranks must start from the same weights. The returned sums are the global ones."""
 
     def __init__(self, learning_rate: float = DEFAULT_LEARNING_RATE, max_grad_norm: float = DEFAULT_MAX_GRAD_NORM,
-                 weight_decay: float = DEFAULT_WEIGHT_DECAY, shuffle_seed: int | None = None):
+                 weight_decay: float = DEFAULT_WEIGHT_DECAY, shuffle_seed: int | None = None, group=None):
         import torch  # noqa: PLC0415
 
         self.torch = torch
         self.learning_rate, self.max_grad_norm, self.weight_decay = learning_rate, max_grad_norm, weight_decay
         self.shuffle_seed = shuffle_seed  # None: env slices in env order; a seed: PpoLearner's keyed permutation
+        self.group, self.world, self.rank = group, 1, 0
+        if group is not None:
+            import torch.distributed as dist  # noqa: PLC0415
+
+            self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+        if self.world == 1:
+            self.group = None  # one rank: today's path, no collective
+        self._agreed = None              # the update shape the ranks last agreed on
         self._mb = _ShuffledMinibatches()
         self.actor = self.critic = None  # the GruPolicy handles the state below belongs to
         self.step = 0                    # optimizer steps taken
@@ -305,6 +326,31 @@ class HipPpoLearner:
     @staticmethod
     def _handle(p) -> GruPolicy:
         return p.policy if isinstance(p, TrainablePolicy) else p
+
+    def rank_seed(self) -> int | None:
+        """The seed of this rank's minibatch permutation: (shuffle_seed + 0x9E3779B97F4A7C15 rank)
+        mod 2^64. Rank 0's (and a single process's) is shuffle_seed itself; ranks do not shuffle alike."""
+        if self.shuffle_seed is None or self.rank == 0:
+            return self.shuffle_seed
+        return (int(self.shuffle_seed) + RANK_SEED_STRIDE * self.rank) % (1 << 64)
+
+    def check_ranks(self, n_local: int, T: int, batch_size: int, num_passes: int) -> None:
+        """With several ranks: raise ZbError unless batch_size is a multiple of the world size and all
+        ranks agree on (n_local, T, batch_size, num_passes, shuffle_seed, learning_rate) - one small
+        all_gather, no GPU work over gloo. update() runs it once per such shape."""
+        key = (int(n_local), int(T), int(batch_size), int(num_passes))
+        if self.world == 1 or self._agreed == key:
+            return
+        from .dist import agree  # noqa: PLC0415
+
+        seed = -1 if self.shuffle_seed is None else int(self.shuffle_seed) % (1 << 64)
+        lr = struct.unpack("<q", struct.pack("<d", float(self.learning_rate)))[0]
+        agree(dict(n_local=key[0], T=key[1], batch_size=key[2], num_passes=key[3], shuffle=int(seed >= 0),
+                   shuffle_seed_low=seed & 0xFFFFFFFF, shuffle_seed_high=(seed >> 32) & 0xFFFFFFFF if seed >= 0 else 0,
+                   learning_rate_bits=lr), f"HipPpoLearner over {self.world} ranks", self.group)
+        if key[2] % self.world:
+            raise ZbError(f"batch_size {key[2]} is the global one: it must be a multiple of the {self.world} ranks")
+        self._agreed = key
 
     def _bind(self, actor: GruPolicy, critic: GruPolicy) -> None:
         torch = self.torch
@@ -336,6 +382,10 @@ class HipPpoLearner:
                 self._buf[net] = dict(grad=torch.empty(cnt, dtype=torch.float32, device=dev),
                                       part=torch.empty(max(int(L.zb_sqnorm_partials_words(cnt)), 1),
                                                        dtype=torch.float64, device=dev))
+                if self.world > 1:  # the all-gather's destination: every rank's gradient, rank order
+                    self._buf[net]["rows"] = torch.empty(self.world, cnt, dtype=torch.float32, device=dev)
+            if self.world > 1:
+                self._buf["sums"] = torch.empty(self.world, 4, dtype=torch.float64, device=dev)
 
     def update(self, rollout: dict, ppo_inputs, actor, critic, actor_carry0, critic_carry0, reset=None,
                num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, **loss_kw) -> list:
@@ -353,7 +403,14 @@ class HipPpoLearner:
                                         self._buf["actor"], self._buf["critic"], self._buf["sq"])
         T = rollout["actions"].shape[0]
         n = rollout["actions"].shape[1]
+        W = self.world
+        if W > 1:
+            from .dist import all_gather_rows  # noqa: PLC0415
+
+            self.check_ranks(n, T, batch_size, num_passes)
+            batch_size //= W  # this rank's share of every minibatch
         shuffled = self.shuffle_seed is not None
+        seed = self.rank_seed()
         if reset is None and not shuffled:
             reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
             reset[1:] = rollout["done"][:T - 1]
@@ -370,7 +427,7 @@ class HipPpoLearner:
 
                 if shuffled:
                     mb = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo, hi - lo,
-                                      self.shuffle_seed, self.epoch)
+                                      seed, self.epoch)
                     obs_a, acts, obs_c, rs, ca, cc = mb["obs_a"], mb["acts"], mb["obs_c"], mb["rs"], mb["ca"], mb["cc"]
                     old_lp, adv, old_v, vt = mb["old_lp"], mb["adv"], mb["old_v"], mb["vt"]
                 else:
@@ -379,17 +436,28 @@ class HipPpoLearner:
                 lp, scr_a = act.actor_train(obs_a, acts, ca, rs)
                 v, scr_c = cri.critic_train(obs_c, cc, rs)
                 sums = torch.empty(6, dtype=torch.float64, device=lp.device)
-                sums[4], sums[5] = float(T * (hi - lo)), coef
+                total = T * (hi - lo) * W  # the rows of this minibatch on all ranks
+                sums[4], sums[5] = float(total), coef
                 if not shuffled:
                     old_lp, adv, old_v, vt = (cut(rollout["log_prob"]), cut(ppo_inputs.advantages_t),
                                               cut(rollout["value"]), cut(ppo_inputs.value_targets_t))
-                d_lp, d_v, _ = ppo.ppo_loss_grad(lp, old_lp, adv, v, old_v, vt, sums=sums, **loss_kw)
+                d_lp, d_v, _ = ppo.ppo_loss_grad(lp, old_lp, adv, v, old_v, vt, sums=sums,
+                                                 **(loss_kw if W == 1 else dict(loss_kw, total=total)))
                 # the critic first: its saved activations were written last, so more of them are still in
                 # the cache (autograd runs PpoLearner's backward passes in this order too)
                 cri.critic_backward(obs_c, cc, rs, d_v, scr_c, grad=bc["grad"])
                 act.actor_backward(obs_a, acts, ca, rs, d_lp, scr_a, grad=ba["grad"])
-                ppo.grad_sqnorm(ba["grad"], out=sq[0:1], partials=ba["part"])
-                ppo.grad_sqnorm(bc["grad"], out=sq[1:2], partials=bc["part"])
+                if W == 1:
+                    ppo.grad_sqnorm(ba["grad"], out=sq[0:1], partials=ba["part"])
+                    ppo.grad_sqnorm(bc["grad"], out=sq[1:2], partials=bc["part"])
+                else:  # the sum over ranks in rank order, and its squared norm, the same bits on every rank
+                    for k, b in enumerate((ba, bc)):
+                        all_gather_rows(b["grad"], b["rows"], self.group)
+                        ppo.grad_combine(b["rows"], out=b["grad"], sq_out=sq[k:k + 1], partials=b["part"])
+                    g = all_gather_rows(sums[:4], self._buf["sums"], self.group)
+                    sums[:4].copy_(g[0])  # then + rank 1, + rank 2, ...: rank order, on the device
+                    for r in range(1, W):
+                        sums[:4] += g[r]
                 self.step += 1
                 for st, b, tail in ((sa, ba, JOINTS), (sc, bc, 0)):
                     ppo.adamw_step(st["params"], b["grad"], st["m"], st["v"], sq, self.step, self.learning_rate,
@@ -411,15 +479,19 @@ class HipPpoLearner:
         return -sums[0] / sums[4] + sums[5] * 0.5 * sums[1] / sums[4]
 
     def state_dict(self) -> dict:
-        """{"step", "epoch", "actor": {"params", "m", "v"}, "critic": {...}} (copies)."""
+        """{"step", "epoch", "world", "actor": {"params", "m", "v"}, "critic": {...}} (copies)."""
         if self.state is None:
             raise ZbError("HipPpoLearner.state_dict(): no state yet (no update() and no load_state_dict())")
-        return dict(step=self.step, epoch=self.epoch, **{net: {k: t.clone() for k, t in self.state[net].items()}
-                                       for net in ("actor", "critic")})
+        return dict(step=self.step, epoch=self.epoch, world=self.world,
+                    **{net: {k: t.clone() for k, t in self.state[net].items()} for net in ("actor", "critic")})
 
     def load_state_dict(self, sd: dict) -> None:
         """Restore state_dict()'s result. The next update() pushes the restored parameters to the
-        handles it is given and continues the step count."""
+        handles it is given and continues the step count. A state saved at another world size is
+        refused: its minibatches were cut differently."""
+        if int(sd.get("world", 1)) != self.world:  # a state dict from before the multi-rank update has none
+            raise ZbError(f"the state was saved by a learner over {sd.get('world', 1)} rank(s); this one runs over "
+                          f"{self.world}")
         self.state = {net: {k: sd[net][k].clone() for k in ("params", "m", "v")} for net in ("actor", "critic")}
         self.step = int(sd["step"])
         self.epoch = int(sd.get("epoch", 0))  # a state dict from before the shuffle has none

@@ -260,6 +260,52 @@ def grad_sqnorm(grad, out=None, partials=None):
     return out
 
 
+COMBINE_MAX_WORLD = 64  # ZB_COMBINE_MAX_WORLD
+
+
+def grad_combine(parts, out=None, sq_out=None, partials=None):
+    """zb_grad_combine: the sum over ranks of an all-gathered gradient, by the fixed fp64 tree in rank
+    order. parts [world, count] float32 on the device, contiguous (zbot_amd.dist.all_gather_rows'
+    destination) -> (out [count] float32, sq_out [1] float64): the sum rounded to float32 once, and
+    the bits grad_sqnorm(out) would return. `out` must not overlap `parts`; the optional outputs and
+    the `partials` scratch (as grad_sqnorm's) are reused when given."""
+    import torch  # noqa: PLC0415
+
+    L = load_library()
+    dev = parts.device
+    if dev.type != "cuda":
+        raise ZbError("ppo.grad_combine runs on the GPU (libzbot_hip.so); grad_combine_host is the CPU twin")
+    if _f32_dev(parts, dev, torch, "parts").dim() != 2:
+        raise ZbError(f"parts must be [world, count], got {list(parts.shape)}")
+    world, count = parts.shape
+    if out is None:
+        out = torch.empty(count, dtype=torch.float32, device=dev)
+    elif _f32_dev(out, dev, torch, "out").numel() != count:
+        raise ZbError(f"out must hold {count} elements")
+    words = int(L.zb_sqnorm_partials_words(count))
+    partials = (torch.empty(max(words, 1), dtype=torch.float64, device=dev) if partials is None
+                else _f64_dev(partials, dev, torch, "partials", words))
+    sq_out = (torch.empty(1, dtype=torch.float64, device=dev) if sq_out is None
+              else _f64_dev(sq_out, dev, torch, "sq_out", 1))
+    with torch.cuda.device(dev):
+        _check(L.zb_grad_combine(parts.data_ptr(), int(world), int(count), out.data_ptr(), partials.data_ptr(),
+                                 sq_out.data_ptr(), _stream(torch, dev)))
+    return out, sq_out
+
+
+def grad_combine_host(parts):
+    """zb_grad_combine_host: the same trees on the CPU, the kernel's bit definition.
+    parts [world, count] float32 (numpy or a CPU tensor) -> (grad [count] float32 numpy, squared norm float)."""
+    import numpy as np  # noqa: PLC0415
+
+    p = _host(parts, np.float32, "parts")
+    if p.ndim != 2:
+        raise ZbError(f"parts must be [world, count], got {list(p.shape)}")
+    grad, sq = np.empty(p.shape[1], np.float32), np.empty(1, np.float64)
+    _check(load_library().zb_grad_combine_host(p.ctypes.data, p.shape[0], p.shape[1], grad.ctypes.data, sq.ctypes.data))
+    return grad, float(sq[0])
+
+
 def adamw_step(param, grad, m, v, sqnorms, step: int, lr: float, max_grad_norm: float = 0.0,
                weight_decay: float = 0.0, frozen_tail: int = 0, beta1: float = ADAM_BETA1, beta2: float = ADAM_BETA2,
                eps: float = ADAM_EPS) -> None:

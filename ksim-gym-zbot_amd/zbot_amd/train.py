@@ -3,9 +3,16 @@ from the library's blocks: rollout with the GRU actor and the in-loop critic, PP
 update in HIP, the episode-length curriculum.
 
     tr = Trainer(engine, actor, critic, rollout_steps=200, num_passes=4, batch_size=128,
-                 seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, **learner_kw)
+                 seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, group=None,
+                 **learner_kw)
     m = tr.step()            # one iteration; returns metrics
     sd = tr.state_dict(); tr.load_state_dict(sd)
+
+Several GPUs: one Trainer per rank over its shard of the envs (engine.env_offset = rank x engine.n)
+and `group` = the ranks' torch.distributed process group. `batch_size` is then the global one; the
+advantage moments, the gradients (summed in rank order by ppo.grad_combine), the loss sums, the
+episode length and so the curriculum level are global, and every rank holds the same weights bit for
+bit. The state dict stays per rank.
 
 `engine` is a HipEngine or an EnvGroups, `actor` / `critic` are GruPolicy handles; the remaining
 keyword arguments go to HipPpoLearner (learning_rate, max_grad_norm, weight_decay). Saving to a file
@@ -36,7 +43,7 @@ DEFAULT_ROLLOUT_STEPS = 200  # rollout_length_seconds 4.0 / ctrl_dt 0.02 (train.
 
 
 class Trainer:
-    """One training process on one GPU: owns the PolicyRollout, the critic's carry, the
+    """One training process on one GPU (one rank of `group`, when given): owns the PolicyRollout, the critic's carry, the
     HipPpoLearner and the curriculum state. The seed keys the actor's action samples and, with
     shuffle, the minibatch permutation (shuffle=False: env slices in env order). Everything runs
     on the current stream; two Trainers built from the same seeds, weights and engine seed produce
@@ -45,7 +52,7 @@ class Trainer:
     def __init__(self, engine, actor: GruPolicy, critic: GruPolicy, rollout_steps: int = DEFAULT_ROLLOUT_STEPS,
                  num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, seed: int = 0,
                  shuffle: bool = True, curriculum: EpisodeLengthCurriculum | None = None, ctrl_dt: float = 0.02,
-                 **learner_kw):
+                 group=None, **learner_kw):
         if actor.kind != ACTOR or critic.kind == ACTOR:
             raise ZbError("Trainer(engine, actor, critic): an actor and a critic handle, in this order")
         if rollout_steps < 1 or num_passes < 1 or batch_size < 1:
@@ -54,11 +61,24 @@ class Trainer:
         self.eng, self.actor, self.critic = engine, actor, critic
         self.T, self.num_passes, self.batch_size = int(rollout_steps), int(num_passes), int(batch_size)
         self.seed, self.shuffle, self.ctrl_dt = int(seed), bool(shuffle), float(ctrl_dt)
+        self.group, self.world, self.rank = group, 1, 0
+        if group is not None:
+            import torch.distributed as dist  # noqa: PLC0415
+
+            from .dist import agree  # noqa: PLC0415
+
+            self.world, self.rank = dist.get_world_size(group), dist.get_rank(group)
+            if int(engine.env_offset) != self.rank * int(engine.n):
+                raise ZbError(f"rank {self.rank} of {self.world} owns envs from {self.rank * int(engine.n)}: the engine "
+                              f"was created with env_offset {engine.env_offset}")
+            agree(dict(seed=self.seed % (1 << 63), shuffle=int(self.shuffle), rollout_steps=self.T,
+                       num_passes=self.num_passes, batch_size=self.batch_size, envs_per_rank=int(engine.n)),
+                  f"Trainer over {self.world} ranks", group)
         self.curriculum = EpisodeLengthCurriculum() if curriculum is None else curriculum
         self.cur_state = self.curriculum.initial_state()
         self.rollout = PolicyRollout(engine, actor, seed=self.seed, curriculum=self.cur_state.level)
         self.critic_carry = critic.initial_carry(engine.n)
-        self.learner = HipPpoLearner(shuffle_seed=self.seed if self.shuffle else None, **learner_kw)
+        self.learner = HipPpoLearner(shuffle_seed=self.seed if self.shuffle else None, group=group, **learner_kw)
         self.iteration = 0
         self.last_rollout = None  # the last step()'s rollout dict and PPO inputs, for inspection
         self.last_inputs = None
@@ -74,7 +94,7 @@ class Trainer:
 
     def step(self) -> dict:
         """One training iteration. Returns {"iteration", "level" (the level the rollout ran at),
-        "episode_length" (seconds, a float), "reward" (mean per env-step), "loss", "clip_fraction",
+        "episode_length" (seconds, a float), "reward" (mean per env-step, over all ranks), "loss", "clip_fraction",
         "approx_kl" ([optimizer steps] each), "sums" (HipPpoLearner.update's list)}; the tensors are
         on the device and nothing but the episode length is synchronised."""
         torch = self.torch
@@ -91,7 +111,7 @@ class Trainer:
         self._mark("rollout", True)
         self._mark("ppo_inputs", False)
         inputs = ppo.compute_ppo_inputs(out["value"], out["reward"], out["done"], out["success"],
-                                        bootstrap=out["value_next"])
+                                        bootstrap=out["value_next"], group=self.group)
         self._mark("ppo_inputs", True)
         reset = None
         if prev_done is not None:
@@ -100,12 +120,21 @@ class Trainer:
         sums = self.learner.update(out, inputs, self.actor, self.critic, carry0, ccarry0, reset=reset,
                                    num_passes=self.num_passes, batch_size=self.batch_size)
         self._mark("update", True)
-        length = rollout_episode_length(self.eng.get_stats(), self.eng.get_state(), out["done"][T - 1], self.ctrl_dt)
+        length = rollout_episode_length(self.eng.get_stats(), self.eng.get_state(), out["done"][T - 1], self.ctrl_dt,
+                                        group=self.group)
         self.cur_state = self.curriculum.update(self.cur_state, length)
         self.iteration += 1
         self.last_rollout, self.last_inputs = out, inputs
         s = torch.stack(sums)
-        return dict(iteration=self.iteration, level=level, episode_length=length, reward=out["reward"].mean(),
+        reward = out["reward"].mean()
+        if self.world > 1:  # the mean over every rank's env-steps: float64 sums, added in rank order
+            from .dist import reduce_fixed_order  # noqa: PLC0415
+
+            r = out["reward"]
+            tot = reduce_fixed_order(torch.stack([r.double().sum(), torch.tensor(float(r.numel()), dtype=torch.float64,
+                                                                               device=r.device)]), group=self.group)
+            reward = tot[0] / tot[1]
+        return dict(iteration=self.iteration, level=level, episode_length=length, reward=reward,
                     loss=-s[:, 0] / s[:, 4] + s[:, 5] * 0.5 * s[:, 1] / s[:, 4], clip_fraction=s[:, 2] / s[:, 4],
                     approx_kl=s[:, 3] / s[:, 4], sums=sums)
 
@@ -129,7 +158,7 @@ class Trainer:
             params=dict(actor=self.actor.params_tensor(), critic=self.critic.params_tensor()),
             learner=None if self.learner.state is None else self.learner.state_dict(),
             curriculum=dict(level=float(self.cur_state.level), steps=int(self.cur_state.steps)),
-            iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle)
+            iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle, world=self.world, rank=self.rank)
 
     def load_state_dict(self, sd: dict) -> None:
         """Restore state_dict()'s result into this Trainer's engine, handles and learner."""
@@ -141,6 +170,9 @@ class Trainer:
                           f"seed {self.eng.seed}")
         if int(sd["seed"]) != self.seed or bool(sd["shuffle"]) != self.shuffle:
             raise ZbError(f"the state was trained with seed={sd['seed']}, shuffle={sd['shuffle']}")
+        if int(sd.get("world", 1)) != self.world or int(sd.get("rank", 0)) != self.rank:
+            raise ZbError(f"the state is rank {sd.get('rank', 0)}'s of {sd.get('world', 1)}; this Trainer is rank "
+                          f"{self.rank} of {self.world}")
         self.eng.set_state(e["state"])
         self.eng.set_rand(e["rand"])
         ro, r = self.rollout, sd["rollout"]
@@ -151,7 +183,7 @@ class Trainer:
         self.critic_carry.copy_(sd["critic_carry"])
         self.learner = HipPpoLearner(learning_rate=self.learner.learning_rate, max_grad_norm=self.learner.max_grad_norm,
                                      weight_decay=self.learner.weight_decay,
-                                     shuffle_seed=self.seed if self.shuffle else None)
+                                     shuffle_seed=self.seed if self.shuffle else None, group=self.group)
         # the next rollout comes before the next update: the handles need the weights now
         self.actor.set_params(sd["params"]["actor"].to(dev, dtype=torch.float32))
         self.critic.set_params(sd["params"]["critic"].to(dev, dtype=torch.float32))
