@@ -200,6 +200,7 @@ static zb::StepArgs base_args(ZbHandle* h) {
   a.solver = h->cfg.solver;
   a.xg = h->xg;
   a.ed = (h->cfg.flags & ZB_F_EULERDAMP) ? 1 : 0;
+  a.sol_default = zb::solver_fields_default(h->cfg) ? 1 : 0;
   a.xj = h->xj;
   return a;
 }

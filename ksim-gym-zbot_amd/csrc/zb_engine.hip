@@ -729,6 +729,36 @@ __device__ __forceinline__ uint64_t cseed(const Ctx& c) {
 }
 __device__ __forceinline__ uint32_t cenv(const Ctx& c) { return c.L->s.env; }
 
+/* The solver fields of the config where the solver loops read them. DS: the handle's fields are the
+   defaults (zb_internal.h solver_fields_default, checked by the host at every launch), held as
+   literals: no load, and the compiler knows the loops' trip counts. Otherwise the config's scalar
+   load where the loop tests it. The step kernels with a DS copy: SOL_LITERAL. */
+template <bool DS>
+__device__ __forceinline__ int sol_iterations(CP cfg) {
+  if constexpr (DS) return SOL_DEFAULT_ITERATIONS;
+  else return cfg->iterations;
+}
+template <bool DS>
+__device__ __forceinline__ int sol_ls_iterations(CP cfg) {
+  if constexpr (DS) return SOL_DEFAULT_LS_ITERATIONS;
+  else return cfg->ls_iterations;
+}
+template <bool DS>
+__device__ __forceinline__ float sol_tolerance(CP cfg) {
+  if constexpr (DS) return SOL_DEFAULT_TOLERANCE;
+  else return cfg->tolerance;
+}
+template <bool DS>
+__device__ __forceinline__ float sol_ls_tolerance(CP cfg) {
+  if constexpr (DS) return SOL_DEFAULT_LS_TOLERANCE;
+  else return cfg->ls_tolerance;
+}
+/* the step kernels that exist in a second copy with the default solver fields as literals: the two-sole
+   kernels with explicit damping, CG (the headline) and Newton, where the copy was measured
+   (profiles/const_wait_ab_*.log). Every other handle runs its generic kernel */
+template <int SOLVER, int XG, int ED>
+constexpr bool SOL_LITERAL = XG == 0 && ED == 0;
+
 /* ancestor dof at depth e of a dof whose limb chain starts at dof `head`
    (root dofs: head < 0): the tree shape makes ancestors dofs 0..NROOT-1
    followed by a contiguous run of the limb (e past the depth: a valid dummy) */
@@ -3238,7 +3268,7 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
 /* exact line search along `search`; returns alpha (team-uniform) and Mv/Jv.
    ZL: search, Ma, fs and grad are exact zeros on the lanes past the dofs (solve_cg): their products
    are zeros without a mask */
-template <int XG, bool XA = true, bool ZL = false>
+template <int XG, bool XA = true, bool ZL = false, bool DS = false>
 __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float jr[CAP], float search, float Ma, float fs,
                                              float grad, float& Mv) {
   CP cfg = c.cfg;
@@ -3303,7 +3333,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
               DZJ2 = (ZPAIR<XG> && XA) ? DZJ * r.z.Jv : 0.f;
   float d1 = cc[2], d2 = c2 + cc[3];
   if (!(d1 < 0.f) || !(d2 > 0.f)) return 0.f;
-  const float gtol = cfg->ls_tolerance * (-d1);
+  const float gtol = sol_ls_tolerance<DS>(cfg) * (-d1);
   /* the iteration loop in two copies, with and without the joint-limit row (LIM): a branch on
      r.anyl inside the evaluation is if-converted by the compiler into selects around the row's
      arithmetic, which then runs in every evaluation */
@@ -3357,7 +3387,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
     };
     float lo = 0.f, hi = -1.f;
     float alpha = -d1 / d2;
-    for (int it = 0; it < cfg->ls_iterations; it++) {
+    for (int it = 0; it < sol_ls_iterations<DS>(cfg); it++) {
       eval(alpha, d1, d2);
       if (fabsf(d1) <= gtol) break;
       if (d1 < 0.f) lo = alpha; else hi = alpha;
@@ -3470,7 +3500,7 @@ __device__ __forceinline__ float hsolve_pair(const Ctx& c, const Rows& r, const 
 }
 
 /* constrained acceleration (mj_solNewton, primal). Returns qacc (dof lane). */
-template <int XG, bool XA = true>
+template <int XG, bool XA = true, bool DS = false>
 __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, float fs, float w, int& iters,
                                               bool live, float& ftot) {
   CP cfg = c.cfg;
@@ -3555,10 +3585,10 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
   else search = -solve_ldl(c, grad, Dinv);
   STAMP(S_SOLVE0);
   int it = 0;
-  while (live && it < cfg->iterations) {
+  while (live && it < sol_iterations<DS>(cfg)) {
     float Mv;
     STAMP(S_CHECK);
-    float alpha = line_search<XG, XA>(c, r, jr, search, Ma, fs, grad, Mv);
+    float alpha = line_search<XG, XA, false, DS>(c, r, jr, search, Ma, fs, grad, Mv);
     STAMP(S_LS);
     if (alpha == 0.f) break;
     x += alpha * search;
@@ -3589,7 +3619,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
        them here (qacc, forces and costs are the same bits either way). */
     const float improvement = scale * (oldcost - cost);
     const float gradient = scale * sqrtf(red[1]);
-    if (improvement < cfg->tolerance || gradient < cfg->tolerance || it >= cfg->iterations) break;
+    if (improvement < sol_tolerance<DS>(cfg) || gradient < sol_tolerance<DS>(cfg) || it >= sol_iterations<DS>(cfg)) break;
     /* H depends only on the active set (M, D fixed within a substep):
        refactor only when it changed (MuJoCo's Newton does the same) */
     const bool changed = red[2] > 0.f;
@@ -3620,7 +3650,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
    forces, no implicit_damping reads ftot). The iteration at the cap then ends with its step.
    FOLD, GN: the masks folded into data (below; solve_prep's GN). forward() leaves them off for the
    few instantiations that spilled more vector registers with them. */
-template <int XG, bool XA = true, bool FOLD = true, bool GN = true>
+template <int XG, bool XA = true, bool FOLD = true, bool GN = true, bool DS = false>
 __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float fs, float w, int& iters, bool live,
                                           float DinvM, float& ftot, bool qacc_only) {
   CP cfg = c.cfg;
@@ -3706,11 +3736,11 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   STAMP(S_SOLVE0);
   float search = -mg;
   int it = 0;
-  const int itmax = cfg->iterations;
+  const int itmax = sol_iterations<DS>(cfg);
   while (live && it < itmax) {
     float Mv;
     STAMP(S_CHECK);
-    const float alpha = line_search<XG, XA, FOLD>(c, r, jr, search, Ma, fs, grad, Mv);
+    const float alpha = line_search<XG, XA, FOLD, DS>(c, r, jr, search, Ma, fs, grad, Mv);
     STAMP(S_LS);
     if (alpha == 0.f) break;
     /* x and r.jf (below) take the same product in two blocks since the exit between them, and the
@@ -3754,7 +3784,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
       cost = red[0];
       const float improvement = scale * (oldcost - cost);
       const float gradient = scale * sqrtf(red[1]);
-      if (improvement < cfg->tolerance || gradient < cfg->tolerance) break;
+      if (improvement < sol_tolerance<DS>(cfg) || gradient < sol_tolerance<DS>(cfg)) break;
       const float beta = fmaxf(red[2] / fmaxf(red[3], MINVAL), 0.f);
       search = -mg + beta * search;
     } else {
@@ -3812,7 +3842,7 @@ __device__ __forceinline__ void feetech(const Ctx& c, LaneS& ls) {
    VALU diet"): the pointer-jumping schedules from Ctx::pjb / pjd, masks folded into data (the mass
    scale, the cdof rows, lane ZLANE's zeros).
    Bit-identical to the forms they replace, which the other instantiations keep. */
-template <int SOLVER, int XG, bool FQ = true, bool SD = false>
+template <int SOLVER, int XG, bool FQ = true, bool SD = false, bool DS = false>
 __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, BodyK& B, Rows& r, bool with_sensors,
                                         Sensors& sen, int& iters) {
   MP m = c.m;
@@ -3876,8 +3906,8 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
     auto solve = [&](auto xa) -> float {
       constexpr bool XA = decltype(xa)::value;
       return SOLVER == ZB_SOLVER_CG
-                 ? solve_cg<XG, XA, FOLD, GN>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
-                 : solve_newton<XG, XA>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
+                 ? solve_cg<XG, XA, FOLD, GN, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
+                 : solve_newton<XG, XA, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
     };
     const bool xa = XG != 0 && (r.x.any || (YBANK<XG> && r.y.any) || (ZPAIR<XG> && r.z.any)); /* wave-uniform */
     const float qn = xa ? solve(BoolC<true>{}) : solve(BoolC<false>{});
@@ -4597,7 +4627,8 @@ template <int SOLVER, int XG, bool ED>
 constexpr bool SMOOTH_DIET = SOLVER == ZB_SOLVER_CG
                                  ? (XG == 0 || XG == 5 || (XG == 1 && !ED) || (XG == 2 && ED) || (XG == 3 && ED))
                                  : (XG == 0 || XG == 2 || XG == 5);
-template <int SOLVER, int XG, int ED>
+/* DS: the copy for handles whose solver fields are the defaults (sol_iterations; SOL_LITERAL) */
+template <int SOLVER, int XG, int ED, bool DS = false>
 __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const int team = threadIdx.x / TEAM;
   /* Chunked step (a.nchunk > 1, one control step): the launch has npair * nchunk workgroups, each
@@ -4708,7 +4739,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (!resetting && !ghost) feetech<XG>(c, ls);
       STAMP(S_FEETECH);
       int it_pass = 0;
-      forward<SOLVER, XG, ED != 0, SD>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
+      forward<SOLVER, XG, ED != 0, SD, DS>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
       if (!ghost) iters += it_pass;
       if (!resetting && !ghost) {
         /* wave-uniform: both teams integrate, or both run the reset / ghost pass */
@@ -4993,7 +5024,14 @@ hipError_t ZB_EP(launch_step)(const StepArgs& a, hipStream_t s) {
 #endif
   dim3 grid((unsigned)((b.n_envs + NTEAM - 1) / NTEAM * b.nchunk)), block(64);
   with_variant(b.solver, b.xg, b.ed, [&](auto S, auto X, auto D) {
-    hipLaunchKernelGGL((step_kernel<decltype(S)::value, decltype(X)::value, decltype(D)::value>), grid, block, 0, s, b);
+    constexpr int SV = decltype(S)::value, XV = decltype(X)::value, DV = decltype(D)::value;
+    if constexpr (SOL_LITERAL<SV, XV, DV>) {
+      if (b.sol_default) {
+        hipLaunchKernelGGL((step_kernel<SV, XV, DV, true>), grid, block, 0, s, b);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((step_kernel<SV, XV, DV>), grid, block, 0, s, b);
   });
   return hipGetLastError();
 }

@@ -61,7 +61,22 @@ struct StepArgs {
   int xg;                   /* general colliders (zb_host.h needs_xg): 0 two-sole, 1 two banks, 2 two banks + cylinders / ellipsoids / meshes, 3 / 4 the sole pair, 5 three banks of floor colliders, 6 those and the sole pair's fourth */
   float* xj;                /* xg: [n + 1, banks x ZB_XJ_STRIDE] Jacobian rows of the banks beyond the first (1 to 3 blocks per env; the last env block: ghost teams) */
   int ed;                   /* ZB_F_EULERDAMP: the step kernel integrates the joint damping implicitly */
+  int sol_default;          /* the handle's solver fields are the defaults (solver_fields_default): launch_step may
+                               run the instantiation that holds them as literals */
 };
+
+/* The solver fields of zb_default_config (MuJoCo's opt.tolerance / ls_tolerance defaults, train.py's
+   iteration counts). A handle's config never changes after zb_create, so zb_capi.cpp compares it with
+   these once per launch on the host copy, and step_kernel<.., DS = true> holds them as literals: its
+   solver loops load no config field. Any other value runs the generic instantiation. */
+constexpr int SOL_DEFAULT_ITERATIONS = 8;
+constexpr int SOL_DEFAULT_LS_ITERATIONS = 8;
+constexpr float SOL_DEFAULT_TOLERANCE = 1e-8f;
+constexpr float SOL_DEFAULT_LS_TOLERANCE = 0.01f;
+inline bool solver_fields_default(const ZbEnvConfig& c) {
+  return c.iterations == SOL_DEFAULT_ITERATIONS && c.ls_iterations == SOL_DEFAULT_LS_ITERATIONS &&
+         c.tolerance == SOL_DEFAULT_TOLERANCE && c.ls_tolerance == SOL_DEFAULT_LS_TOLERANCE;
+}
 
 /* workgroups of step_kernel resident on the device at once (occupancy x CUs) */
 int step_resident_blocks(int device, int xg, int solver, int ed);
