@@ -577,13 +577,55 @@ typedef __attribute__((address_space(1))) xv4f gfloat4_t;
 __device__ __forceinline__ gfloat_t* xrows(const EnvL* L) {
   return (gfloat_t*)(((uint64_t)L->s.xj_hi << 32) | (uint64_t)L->s.xj_lo);
 }
-/* XG 4 / 5: the third bank's rows follow the second bank's in the env's block */
-__device__ __forceinline__ gfloat_t* yrows(const EnvL* L) { return xrows(L) + 32 * CAP; }
-/* XG 6: the fourth bank's rows (the sole pair's half rows) follow the third bank's */
-__device__ __forceinline__ gfloat_t* zrows(const EnvL* L) { return xrows(L) + 2 * 32 * CAP; }
-/* floats of StepArgs::xj per env: one [32][CAP] block per extra bank */
+/* What the contact-row banks beyond the soles' hold, by kernel instantiation (zb_host.cpp needs_xg):
+   nothing, floor colliders (two of those beyond the soles within reach of the floor, select_bank2),
+   or the sole pair's half rows (the two box soles against each other, pair_rows). Extra bank B (0..2)
+   is the second, third or fourth bank of the comments and of DESIGN.md. The banks an XG has come
+   first, floor banks before the pair's:
+     XG 0  the two soles alone
+     XG 1  one floor bank
+     XG 2  one floor bank, with the XRICH collider rules
+     XG 3  the sole pair
+     XG 4  one floor bank, then the pair
+     XG 5  two floor banks (models with more than two colliders beyond the soles: the first four within reach)
+     XG 6  two floor banks, then the pair
+   for_banks runs a body over an XG's banks. Code marked "per bank, written out" stays bank by bank: as a
+   for_banks body it compiled to other instructions in the kernels DESIGN.md section 4l names
+   (scripts/isa_diff.py). */
+constexpr int XBANKS = 3;
+enum BankKind { BK_NONE, BK_FLOOR, BK_PAIR };
+constexpr BankKind BANK_KIND[7][XBANKS] = {
+    {BK_NONE, BK_NONE, BK_NONE},   {BK_FLOOR, BK_NONE, BK_NONE}, {BK_FLOOR, BK_NONE, BK_NONE},
+    {BK_PAIR, BK_NONE, BK_NONE},   {BK_FLOOR, BK_PAIR, BK_NONE}, {BK_FLOOR, BK_FLOOR, BK_NONE},
+    {BK_FLOOR, BK_FLOOR, BK_PAIR}};
+template <int XG, int B>
+constexpr bool BFLOOR = BANK_KIND[XG][B] == BK_FLOOR;
+template <int XG, int B>
+constexpr bool BPAIR = BANK_KIND[XG][B] == BK_PAIR;
+/* the number of extra banks, and the one that holds the pair (-1: none) */
 template <int XG>
-constexpr int XJ_STRIDE = ZB_XJ_STRIDE * (XG == 6 ? 3 : XG == 4 || XG == 5 ? 2 : 1);
+constexpr int NBANK = (BANK_KIND[XG][0] != BK_NONE) + (BANK_KIND[XG][1] != BK_NONE) + (BANK_KIND[XG][2] != BK_NONE);
+template <int XG>
+constexpr int PAIR_B = BPAIR<XG, 0> ? 0 : BPAIR<XG, 1> ? 1 : BPAIR<XG, 2> ? 2 : -1;
+template <int XG>
+constexpr bool XFLOOR = BFLOOR<XG, 0>; /* floor colliders beyond the soles: the bank geoms are selected per substep */
+template <int XG>
+constexpr bool ANYPAIR = PAIR_B<XG> >= 0;
+/* f(IntC<B>{}) for each bank the XG has, in bank order */
+template <int XG, typename F>
+__device__ __forceinline__ void for_banks(F&& f) {
+  if constexpr (NBANK<XG> > 0) f(IntC<0>{});
+  if constexpr (NBANK<XG> > 1) f(IntC<1>{});
+  if constexpr (NBANK<XG> > 2) f(IntC<2>{});
+}
+/* bank B's rows: one [32][CAP] block per bank in the env's block, in bank order */
+template <int B>
+__device__ __forceinline__ gfloat_t* bank_rows(const EnvL* L) {
+  return xrows(L) + B * 32 * CAP;
+}
+/* floats of StepArgs::xj per env */
+template <int XG>
+constexpr int XJ_STRIDE = ZB_XJ_STRIDE * (NBANK<XG> > 1 ? NBANK<XG> : 1);
 __device__ __forceinline__ void set_xrows(EnvL* L, float* base) {
   L->s.xj_lo = (uint32_t)(uint64_t)base;
   L->s.xj_hi = (uint32_t)((uint64_t)base >> 32);
@@ -813,9 +855,7 @@ struct Rows {
   bool anyl;
   int nrow;
   uint32_t exmask; /* team-uniform: existing contact rows */
-  XRow x;          /* second bank (XG kernels only) */
-  XRow y;          /* third bank: the sole pair beside floor colliders (XG 4), floor colliders (XG 5, 6) */
-  XRow z;          /* fourth bank: the sole pair beside two banks of floor colliders (XG 6 only) */
+  XRow xb[XBANKS]; /* the extra banks (XG kernels only; what each holds: BANK_KIND) */
 };
 
 /* 16-byte LDS row access (rows are 12 floats = 48 B, 16-B aligned) */
@@ -1676,14 +1716,10 @@ __device__ __forceinline__ float row_dot(const Ctx& c, JP Jrow, int chd, int slo
 __device__ __forceinline__ float row_dot(const Ctx& c, const Rows& r, int slot) {
   return row_dot(c, &c.L->u.J[c.l][0], r.chd, slot);
 }
-__device__ __forceinline__ float row_dot_x(const Ctx& c, const Rows& r, int slot) {
-  return row_dot(c, (const gfloat_t*)xrows(c.L) + c.l * CAP, r.x.chd, slot);
-}
-__device__ __forceinline__ float row_dot_y(const Ctx& c, const Rows& r, int slot) {
-  return row_dot(c, (const gfloat_t*)yrows(c.L) + c.l * CAP, r.y.chd, slot);
-}
-__device__ __forceinline__ float row_dot_z(const Ctx& c, const Rows& r, int slot) {
-  return row_dot(c, (const gfloat_t*)zrows(c.L) + c.l * CAP, r.z.chd, slot);
+/* the lane's row of extra bank B */
+template <int B>
+__device__ __forceinline__ float row_dot_bank(const Ctx& c, const Rows& r, int slot) {
+  return row_dot(c, (const gfloat_t*)bank_rows<B>(c.L) + c.l * CAP, r.xb[B].chd, slot);
 }
 
 /* row_dot with the lane's row already in registers (jr) */
@@ -1929,55 +1965,28 @@ __device__ __forceinline__ void row_params(PR solref, PS solimp, float pos, floa
   aref = -bb * vel - kk * imp * pos;
 }
 
-/* The extra contact-row banks by kernel instantiation (zb_host.cpp needs_xg): XG 1 / 2 the second bank
-   (Rows::x) holds the general floor colliders (the first two beyond the soles within reach, select_bank2;
-   XG 2 compiles cylinders, ellipsoids and meshes), XG 3 the sole pair (the two box soles against each
-   other, pair_rows), XG 4 both: the floor colliders in the second bank and the sole pair in a third
-   (Rows::y, round 6), XG 5 (models with more than two colliders beyond the soles) floor colliders in
-   the second and third banks: the first four within reach of the floor each substep. XG 6: XG 5's two
-   floor banks and the sole pair in a fourth (Rows::z), held as XG 4 holds it in the third. XG 0: the
-   two soles alone. */
+/* The collider rules beyond boxes and capsules (cylinder / ellipsoid / mesh) are compiled for these XG:
+   a property of the collider set alone, not of its banks (BANK_KIND) */
 template <int XG>
-constexpr bool XFLOOR = XG == 1 || XG == 2 || XG == 4 || XG == 5 || XG == 6;
-template <int XG>
-constexpr bool XPAIR = XG == 3; /* the pair in the second bank */
-template <int XG>
-constexpr bool YPAIR = XG == 4; /* the pair in the third bank */
-template <int XG>
-constexpr bool ZPAIR = XG == 6; /* the pair in the fourth bank */
-template <int XG>
-constexpr bool YFLOOR = XG == 5 || XG == 6; /* floor colliders in the third bank too */
-template <int XG>
-constexpr bool YBANK = YPAIR<XG> || YFLOOR<XG>; /* the third bank exists */
-template <int XG>
-constexpr bool XRICH = XG == 2 || XG == 4 || XG == 5 || XG == 6; /* cylinder / ellipsoid / mesh rules compiled */
-template <int XG>
-constexpr bool ANYPAIR = XPAIR<XG> || YPAIR<XG> || ZPAIR<XG>;
-/* The bank that holds the sole pair's half rows (ANYPAIR: the second, third or fourth), its Jacobian
-   rows in the env's scratch block, and its static row masks as the two low bits of the result: bits
-   2-3 of the lane's row-mask word where the pair has the second bank (TP_ROWMASK2), else bits 4-5
-   (TP_ROWMASK3). A bank after the first holds either floor colliders or the pair. */
+constexpr bool XRICH = XG == 2 || XG == 4 || XG == 5 || XG == 6;
+/* The bank that holds the sole pair's half rows (ANYPAIR), its Jacobian rows in the env's scratch
+   block, and its static row masks as the two low bits of the result: bits 2-3 of the lane's row-mask
+   word where the pair has the second bank (TP_ROWMASK2), else bits 4-5 (TP_ROWMASK3). */
 template <int XG>
 __device__ __forceinline__ XRow& pair_bank(Rows& r) {
-  if constexpr (ZPAIR<XG>) return r.z;
-  else if constexpr (YPAIR<XG>) return r.y;
-  else return r.x;
+  return r.xb[PAIR_B<XG>];
 }
 template <int XG>
 __device__ __forceinline__ const XRow& pair_bank(const Rows& r) {
-  if constexpr (ZPAIR<XG>) return r.z;
-  else if constexpr (YPAIR<XG>) return r.y;
-  else return r.x;
+  return r.xb[PAIR_B<XG>];
 }
 template <int XG>
 __device__ __forceinline__ gfloat_t* pair_jrows(const EnvL* L) {
-  if constexpr (ZPAIR<XG>) return zrows(L);
-  else if constexpr (YPAIR<XG>) return yrows(L);
-  else return xrows(L);
+  return bank_rows<PAIR_B<XG>>(L);
 }
 template <int XG>
 __device__ __forceinline__ uint32_t pair_rmb(const Ctx& c) {
-  return XPAIR<XG> ? (c.rmb >> 2) : (c.rmb >> 4);
+  return PAIR_B<XG> == 0 ? (c.rmb >> 2) : (c.rmb >> 4);
 }
 
 /* The collider of team lane l in contact-row bank `bank`: geom 2 bank + l / 16 (general colliders), or
@@ -2276,7 +2285,7 @@ __device__ __forceinline__ void contact_rows(const Ctx& c, const EnvS& s, const 
   if (XFLOOR<XG> && bank >= 1 && __ballot(gvalid) == 0ull) {
     /* no geom of the second bank within reach of the floor in either env of the wave (select_bank2):
        no row, the same state as the full test finds, without its shuffles and rotations (the row's
-       chain is read only while the bank has a row: r.x.any) */
+       chain is read only while the bank has a row: r.xb[0].any) */
     r.chd = -1;
     r.kdep = 0;
     r.nrow = 0;
@@ -2705,8 +2714,8 @@ __device__ __forceinline__ void select_bank2(const Ctx& c, const BodyK& B) {
     sel1 = mk ? 1 + __ffs(mk) : -1;
     mk &= mk - 1u;
   }
-  if constexpr (YFLOOR<XG>) {
-    /* XG 5: the third and fourth geoms within reach take the third bank's halves */
+  if constexpr (BFLOOR<XG, 1>) {
+    /* XG 5, 6: the third and fourth geoms within reach take the third bank's halves */
     const int sel2 = mk ? 1 + __ffs(mk) : -1;
     mk &= mk - 1u;
     const int sel3 = mk ? 1 + __ffs(mk) : -1;
@@ -2728,12 +2737,12 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
   CP cfg = c.cfg;
   const int l = c.l;
   contact_rows<XG>(c, s, B, cm, 0, r, &c.L->u.J[l][0]);
-  if constexpr (XG) {
-    if constexpr (XPAIR<XG>) {
-      pair_rows(c, s, B, cm, r.x, xrows(c.L) + l * CAP);
+  if constexpr (XG) { /* per bank, written out */
+    if constexpr (BPAIR<XG, 0>) {
+      pair_rows(c, s, B, cm, r.xb[0], xrows(c.L) + l * CAP);
     } else {
       select_bank2<XG>(c, B);
-      contact_rows<XG>(c, s, B, cm, 1, r.x, xrows(c.L) + l * CAP);
+      contact_rows<XG>(c, s, B, cm, 1, r.xb[0], xrows(c.L) + l * CAP);
       /* the bank's rows on dof l's chain: dof l is an ancestor of (or is) the geom's last dof kd, a
          root dof or one of kd's own limb chain at or above it */
       uint32_t rm = rm_rows(c.rmb >> 2); /* at most two other geoms: zb_create's static mask (geoms 2, 3) */
@@ -2749,15 +2758,15 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
           rm |= on ? (0xFFFFu << (16 * h)) : 0u;
         }
       }
-      r.x.rowmask = rm;
+      r.xb[0].rowmask = rm;
     }
     /* the second bank's work is skipped, bit for bit, while no row of it exists in the wave (the
        usual case: shins and hands off the floor) */
-    r.x.any = __ballot(r.x.ex) != 0ull;
+    r.xb[0].any = __ballot(r.xb[0].ex) != 0ull;
     bool yany = false;
-    if constexpr (YFLOOR<XG>) {
+    if constexpr (BFLOOR<XG, 1>) {
       /* XG 5: the third and fourth geoms within reach in the third bank, row masks as the second's */
-      contact_rows<XG>(c, s, B, cm, 2, r.y, yrows(c.L) + l * CAP);
+      contact_rows<XG>(c, s, B, cm, 2, r.xb[1], bank_rows<1>(c.L) + l * CAP);
       uint32_t rm = 0u;
 #pragma unroll
       for (int h = 0; h < 2; h++) {
@@ -2768,17 +2777,17 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
         const bool on = l < NV && kd >= 0 && l <= kd && (l < NROOT || c.chd == hkd);
         rm |= on ? (0xFFFFu << (16 * h)) : 0u;
       }
-      r.y.rowmask = rm;
-      r.y.any = yany = __ballot(r.y.ex) != 0ull;
+      r.xb[1].rowmask = rm;
+      r.xb[1].any = yany = __ballot(r.xb[1].ex) != 0ull;
     }
-    if constexpr (YPAIR<XG> || ZPAIR<XG>) {
+    if constexpr (BPAIR<XG, 1> || BPAIR<XG, 2>) {
       /* the pair's half rows in the bank after the floor colliders' (the third: XG 4, the fourth: XG 6) */
       XRow& p = pair_bank<XG>(r);
       pair_rows(c, s, B, cm, p, pair_jrows<XG>(c.L) + l * CAP);
       p.any = __ballot(p.ex) != 0ull;
       yany = yany || p.any;
     }
-    if (r.x.any || yany) {
+    if (r.xb[0].any || yany) {
       /* the rows just stored are read by other lanes from here on */
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2861,7 +2870,7 @@ __device__ __forceinline__ float eval_one(float jar, float D, float& force, int&
   return on ? 0.5f * D * jar * jar : 0.f;
 }
 
-/* row costs at given jar values (no state change); jx: the second bank's contact row (XG) */
+/* row costs at given jar values (no state change); jx, jy, jz: the extra banks' contact rows (XG) */
 template <int XG, bool XA = true>
 __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc, float jf_, float jl_, float jx,
                                            float jy = 0.f, float jz = 0.f) {
@@ -2876,19 +2885,13 @@ __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc
     const float k2 = eval_one(jl_, r.Dl, f, a);
     cost += r.hl ? k2 : 0.f;
   }
-  if constexpr (XG && XA) {
-    const float k3 = eval_one(jx, r.x.D, f, a);
-    /* the sole pair's row is held by two lanes (its halves): counted once */
-    cost += (r.x.ex && (!XPAIR<XG> || c.l < 16)) ? k3 : 0.f;
-  }
-  if constexpr (YBANK<XG> && XA) {
-    const float k4 = eval_one(jy, r.y.D, f, a);
-    cost += (r.y.ex && (YFLOOR<XG> || c.l < 16)) ? k4 : 0.f; /* the pair's halves: once */
-  }
-  if constexpr (ZPAIR<XG> && XA) {
-    const float k5 = eval_one(jz, r.z.D, f, a);
-    cost += (r.z.ex && c.l < 16) ? k5 : 0.f; /* the pair's halves: once */
-  }
+  if constexpr (XA)
+    for_banks<XG>([&](auto b) {
+      constexpr int K = decltype(b)::value;
+      const float k3 = eval_one(K == 0 ? jx : K == 1 ? jy : jz, r.xb[K].D, f, a);
+      /* the sole pair's row is held by two lanes (its halves): counted once */
+      cost += (r.xb[K].ex && (!BPAIR<XG, K> || c.l < 16)) ? k3 : 0.f;
+    });
   return cost;
 }
 
@@ -2987,43 +2990,44 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     if (r.ex) L->rowF[c.l] = r.f;
     L->rowDA[c.l] = (r.ex && r.act) ? r.D : 0.f; /* every row: read by jdj_mfma */
   }
+  /* per bank, written out (and again for the row masks below) */
   float sx0 = 0.f, sx1 = 0.f;
-  if (XG && XA && r.x.any) {
+  if (XG && XA && r.xb[0].any) {
     float f3;
     int a3;
-    const float k3 = eval_one(r.x.jar, r.x.D, f3, a3);
-    cost += (r.x.ex && (!XPAIR<XG> || c.l < 16)) ? k3 : 0.f; /* the pair's halves: once */
-    r.x.f = r.x.ex ? f3 : r.x.f;
-    r.x.act = r.x.ex ? a3 : r.x.act;
-    const float cx = colsum16((const gfloat_t*)xrows(c.L) + c.l * CAP, r.x.ex ? r.x.f : 0.f);
+    const float k3 = eval_one(r.xb[0].jar, r.xb[0].D, f3, a3);
+    cost += (r.xb[0].ex && (!BPAIR<XG, 0> || c.l < 16)) ? k3 : 0.f; /* the pair's halves: once */
+    r.xb[0].f = r.xb[0].ex ? f3 : r.xb[0].f;
+    r.xb[0].act = r.xb[0].ex ? a3 : r.xb[0].act;
+    const float cx = colsum16((const gfloat_t*)xrows(c.L) + c.l * CAP, r.xb[0].ex ? r.xb[0].f : 0.f);
     sx0 = tsh(cx, ddep);
     sx1 = tsh(cx, 16 + ddep);
   }
   float sy0 = 0.f, sy1 = 0.f;
-  if constexpr (YBANK<XG> && XA) {
-    if (r.y.any) {
+  if constexpr ((NBANK<XG> > 1) && XA) {
+    if (r.xb[1].any) {
       float f4;
       int a4;
-      const float k4 = eval_one(r.y.jar, r.y.D, f4, a4);
-      cost += (r.y.ex && (YFLOOR<XG> || c.l < 16)) ? k4 : 0.f; /* the pair's halves: once */
-      r.y.f = r.y.ex ? f4 : r.y.f;
-      r.y.act = r.y.ex ? a4 : r.y.act;
-      const float cy = colsum16((const gfloat_t*)yrows(c.L) + c.l * CAP, r.y.ex ? r.y.f : 0.f);
+      const float k4 = eval_one(r.xb[1].jar, r.xb[1].D, f4, a4);
+      cost += (r.xb[1].ex && (!BPAIR<XG, 1> || c.l < 16)) ? k4 : 0.f; /* the pair's halves: once */
+      r.xb[1].f = r.xb[1].ex ? f4 : r.xb[1].f;
+      r.xb[1].act = r.xb[1].ex ? a4 : r.xb[1].act;
+      const float cy = colsum16((const gfloat_t*)bank_rows<1>(c.L) + c.l * CAP, r.xb[1].ex ? r.xb[1].f : 0.f);
       sy0 = tsh(cy, ddep);
       sy1 = tsh(cy, 16 + ddep);
     }
   }
   float sz0 = 0.f, sz1 = 0.f;
-  if constexpr (ZPAIR<XG> && XA) {
+  if constexpr (BPAIR<XG, 2> && XA) {
     /* XG 6: the pair's half rows in the fourth bank */
-    if (r.z.any) {
+    if (r.xb[2].any) {
       float f5;
       int a5;
-      const float k5 = eval_one(r.z.jar, r.z.D, f5, a5);
-      cost += (r.z.ex && c.l < 16) ? k5 : 0.f; /* the pair's halves: once */
-      r.z.f = r.z.ex ? f5 : r.z.f;
-      r.z.act = r.z.ex ? a5 : r.z.act;
-      const float cz = colsum16((const gfloat_t*)zrows(c.L) + c.l * CAP, r.z.ex ? r.z.f : 0.f);
+      const float k5 = eval_one(r.xb[2].jar, r.xb[2].D, f5, a5);
+      cost += (r.xb[2].ex && (!BPAIR<XG, 2> || c.l < 16)) ? k5 : 0.f; /* the pair's halves: once */
+      r.xb[2].f = r.xb[2].ex ? f5 : r.xb[2].f;
+      r.xb[2].act = r.xb[2].ex ? a5 : r.xb[2].act;
+      const float cz = colsum16((const gfloat_t*)bank_rows<2>(c.L) + c.l * CAP, r.xb[2].ex ? r.xb[2].f : 0.f);
       sz0 = tsh(cz, ddep);
       sz1 = tsh(cz, 16 + ddep);
     }
@@ -3037,17 +3041,17 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     const bool f0 = (c.rmb & 1u) != 0u, f1 = (c.rmb & 2u) != 0u;
     qc = (f0 ? so : 0.f) + (f1 ? sx : 0.f);
     if constexpr (XG && XA) {
-      const uint32_t rm2 = XPAIR<XG> ? rm_rows(c.rmb >> 2) : r.x.rowmask;
+      const uint32_t rm2 = BPAIR<XG, 0> ? rm_rows(c.rmb >> 2) : r.xb[0].rowmask;
       const bool f2 = (rm2 & 0xFFFFu) != 0u, f3 = (rm2 >> 16) != 0u;
       qc += (f2 ? sx0 : 0.f) + (f3 ? sx1 : 0.f);
     }
-    if constexpr (YBANK<XG> && XA) {
+    if constexpr ((NBANK<XG> > 1) && XA) {
       /* the pair's static row masks (XG 4), the third floor bank's of this substep (XG 5) */
-      const bool f4 = YFLOOR<XG> ? (r.y.rowmask & 0xFFFFu) != 0u : (c.rmb & 16u) != 0u;
-      const bool f5 = YFLOOR<XG> ? (r.y.rowmask >> 16) != 0u : (c.rmb & 32u) != 0u;
+      const bool f4 = BFLOOR<XG, 1> ? (r.xb[1].rowmask & 0xFFFFu) != 0u : (c.rmb & 16u) != 0u;
+      const bool f5 = BFLOOR<XG, 1> ? (r.xb[1].rowmask >> 16) != 0u : (c.rmb & 32u) != 0u;
       qc += (f4 ? sy0 : 0.f) + (f5 ? sy1 : 0.f);
     }
-    if constexpr (ZPAIR<XG> && XA) {
+    if constexpr (BPAIR<XG, 2> && XA) {
       /* the pair's static row masks (XG 6: its floor banks' masks are this substep's) */
       const uint32_t pb = pair_rmb<XG>(c);
       qc += ((pb & 1u) != 0u ? sz0 : 0.f) + ((pb & 2u) != 0u ? sz1 : 0.f);
@@ -3070,7 +3074,7 @@ __device__ __forceinline__ float update_constraint(const Ctx& c, Rows& r, const 
  * lane l supplies row 4*chunk + l/16, entry l%16). Staged in the env's L[][]
  * as [foot][12][12]; L[][] is free until factor_ldl writes it. D is rowDA
  * (0 for absent / inactive rows). Wave-uniform: call with every lane active.
- * BANK 1 / 2: the same for the second / third bank's geoms (xrows / yrows J, rowDA holding that bank's
+ * BANK 1 / 2: the same for the second / third bank's geoms (bank_rows<BANK - 1> J, rowDA holding that bank's
  * D), staged in the Hessian rows Hs[][], free until hessian_factor stores the assembled rows. */
 template <int BANK>
 __device__ __forceinline__ void jdj_mfma() {
@@ -3091,9 +3095,9 @@ __device__ __forceinline__ void jdj_mfma() {
         const int r = 16 * f + 4 * ch + k;
         /* no masks: rowDA is zero for absent / inactive rows, and output rows or
            columns e >= CAP (lanes reading entry CAP-1) are never stored */
-        const float jv = BANK == 2   ? yrows(&g_lds[t])[r * CAP + ec]
-                         : BANK == 1 ? xrows(&g_lds[t])[r * CAP + ec]
-                                     : g_lds[t].u.J[r][ec];
+        float jv;
+        if constexpr (BANK >= 1) jv = bank_rows<BANK - 1>(&g_lds[t])[r * CAP + ec];
+        else jv = g_lds[t].u.J[r][ec];
         const float dv = g_lds[t].rowDA[r]; /* BANK >= 1: that bank's, written by hessian_factor */
         acc[t][f] = __builtin_amdgcn_mfma_f32_16x16x4f32(dv * jv, jv, acc[t][f], 0, 0, 0);
       }
@@ -3145,16 +3149,16 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
   const int ddep = vopq(c.ddep);
   EnvL* L = c.L;
   float H[CAP], Hd;
-  uint32_t tb, tb2 = 0u, ch2 = 0u, tb3 = 0u, ch3 = 0u;
+  uint32_t tb, tb2 = 0u, ch2 = 0u, tb3 = 0u, ch3 = 0u; /* the floor banks: per bank, written out */
   float dl2 = 0.f, dl3 = 0.f;
   if (full) {
     Hd = load_mrow(c, H);
     tb = 0u;
     jdj_mfma<0>();
-    if (XFLOOR<XG> && XA && r.x.any) {
+    if (XFLOOR<XG> && XA && r.xb[0].any) {
       /* the second bank's D (rowDA is free once the first bank's J'DJ has read it) */
       tsync();
-      L->rowDA[c.l] = (r.x.ex && r.x.act) ? r.x.D : 0.f;
+      L->rowDA[c.l] = (r.xb[0].ex && r.xb[0].act) ? r.xb[0].D : 0.f;
       tsync();
       jdj_mfma<1>();
     }
@@ -3176,9 +3180,9 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
          so they need no mask */
       for (int e = 0; e < CAP; e++) H[e] += g0[e] + g1[e];
       Hd += d0 + d1;
-      if (XFLOOR<XG> && XA && r.x.any) {
+      if (XFLOOR<XG> && XA && r.xb[0].any) {
         const float* GX = &L->Hs[0][0] + ddep * CAP;
-        const bool f2 = (r.x.rowmask & 0xFFFFu) != 0u, f3 = (r.x.rowmask >> 16) != 0u;
+        const bool f2 = (r.xb[0].rowmask & 0xFFFFu) != 0u, f3 = (r.xb[0].rowmask >> 16) != 0u;
         const float* G2 = f2 ? GX : &L->L[31][0];
         const float* G3 = f3 ? GX + CAP * CAP : &L->L[31][0];
         ld_row(G2, g0);
@@ -3189,16 +3193,16 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
         Hd += d2 + d3;
       }
     }
-    if (YFLOOR<XG> && XA && r.y.any) {
+    if (BFLOOR<XG, 1> && XA && r.xb[1].any) {
       /* XG 5: the third bank's J'DJ through the same staging rows, once the second's are read */
       tsync();
-      L->rowDA[c.l] = (r.y.ex && r.y.act) ? r.y.D : 0.f;
+      L->rowDA[c.l] = (r.xb[1].ex && r.xb[1].act) ? r.xb[1].D : 0.f;
       tsync();
       jdj_mfma<2>();
       tsync();
       if (c.l < NV) {
         const float* GY = &L->Hs[0][0] + ddep * CAP;
-        const bool f4 = (r.y.rowmask & 0xFFFFu) != 0u, f5 = (r.y.rowmask >> 16) != 0u;
+        const bool f4 = (r.xb[1].rowmask & 0xFFFFu) != 0u, f5 = (r.xb[1].rowmask >> 16) != 0u;
         const float* G4 = f4 ? GY : &L->L[31][0];
         const float* G5 = f5 ? GY + CAP * CAP : &L->L[31][0];
         float g4[CAP], g5[CAP];
@@ -3216,15 +3220,15 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
     const float dl = r.ex ? ((r.act ? r.D : 0.f) - (pa ? r.D : 0.f)) : 0.f;
     L->rowF[c.l] = dl; /* rowF is free until the next update_constraint */
     tb = team_ballot(dl != 0.f) & rm_rows(c.rmb);
-    if (XFLOOR<XG> && XA && r.x.any) {
-      dl2 = r.x.ex ? ((r.x.act ? r.x.D : 0.f) - (pa2 ? r.x.D : 0.f)) : 0.f;
+    if (XFLOOR<XG> && XA && r.xb[0].any) {
+      dl2 = r.xb[0].ex ? ((r.xb[0].act ? r.xb[0].D : 0.f) - (pa2 ? r.xb[0].D : 0.f)) : 0.f;
       ch2 = team_ballot(dl2 != 0.f); /* team-uniform: some row of the bank changed */
-      tb2 = ch2 & r.x.rowmask;       /* per dof lane: the changed rows on its chain */
+      tb2 = ch2 & r.xb[0].rowmask;       /* per dof lane: the changed rows on its chain */
     }
-    if (YFLOOR<XG> && XA && r.y.any) {
-      dl3 = r.y.ex ? ((r.y.act ? r.y.D : 0.f) - (pa3 ? r.y.D : 0.f)) : 0.f;
+    if (BFLOOR<XG, 1> && XA && r.xb[1].any) {
+      dl3 = r.xb[1].ex ? ((r.xb[1].act ? r.xb[1].D : 0.f) - (pa3 ? r.xb[1].D : 0.f)) : 0.f;
       ch3 = team_ballot(dl3 != 0.f);
-      tb3 = ch3 & r.y.rowmask;
+      tb3 = ch3 & r.xb[1].rowmask;
     }
     tsync();
   }
@@ -3248,15 +3252,15 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
     tsync();
     if (c.l < NV) add_rows(tb2, (const gfloat_t*)xrows(L), L->rowF, ddep, H, Hd);
   }
-  if (YFLOOR<XG> && ch3 != 0u) {
+  if (BFLOOR<XG, 1> && ch3 != 0u) {
     /* XG 5: the third bank's changed rows, the same way after the second's */
     tsync();
     L->rowF[c.l] = dl3;
     tsync();
-    if (c.l < NV) add_rows(tb3, (const gfloat_t*)yrows(L), L->rowF, ddep, H, Hd);
+    if (c.l < NV) add_rows(tb3, (const gfloat_t*)bank_rows<1>(L), L->rowF, ddep, H, Hd);
   }
   /* the second / third bank's G rows in Hs[] are read before H is stored there */
-  if (XA && full && ((XFLOOR<XG> && r.x.any) || (YFLOOR<XG> && r.y.any))) tsync();
+  if (XA && full && ((XFLOOR<XG> && r.xb[0].any) || (BFLOOR<XG, 1> && r.xb[1].any))) tsync();
   st_row(&L->Hs[c.l][0], H);
   L->Hsd[c.l] = Hd;
   tsync();
@@ -3276,21 +3280,14 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   /* leaves search in vec[V_TMP]; J rows are zero where no contact: no branch around the loads */
   float unused_;
   Mv = mul_m_dot<ZL>(c, r, jr, search, V_TMP, r.Jv, -1, unused_);
-  if constexpr (XG && XA) {
-    float jx = r.x.any ? row_dot_x(c, r, V_TMP) : 0.f;
-    if constexpr (XPAIR<XG>) jx += xor16f(jx); /* the pair's row: both halves */
-    r.x.Jv = jx;
-  }
-  if constexpr (YBANK<XG> && XA) {
-    float jy = r.y.any ? row_dot_y(c, r, V_TMP) : 0.f;
-    if constexpr (YPAIR<XG>) jy += xor16f(jy); /* the pair's row: both halves */
-    r.y.Jv = jy;
-  }
-  if constexpr (ZPAIR<XG> && XA) {
-    float jz = r.z.any ? row_dot_z(c, r, V_TMP) : 0.f;
-    jz += xor16f(jz); /* the pair's row: both halves */
-    r.z.Jv = jz;
-  }
+  if constexpr (XA)
+    for_banks<XG>([&](auto b) {
+      constexpr int K = decltype(b)::value;
+      float j = r.xb[K].any ? row_dot_bank<K>(c, r, V_TMP) : 0.f;
+      if constexpr (BPAIR<XG, K>) j += xor16f(j); /* the pair's row: both halves */
+      r.xb[K].Jv = j;
+    });
+  /* per bank, written out (g20, the DXJ / DYJ / DZJ constants and eval) */
   tsync();
   /* the quadratic's coefficients and the slope/curvature at alpha = 0 in one reduction:
      d1(0) = search . grad (the gradient update_constraint left for the current active
@@ -3300,13 +3297,14 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   float g20 = (r.ex && r.act) ? r.D * r.Jv * r.Jv : 0.f;
   g20 += (r.hf && r.actf) ? r.Df * jv0 * jv0 : 0.f;
   if (r.anyl) g20 += (r.hl && r.actl) ? r.Dl * jv0 * jv0 : 0.f;
-  const bool xprim = !XPAIR<XG> || c.l < 16; /* the lane that counts the second bank's row (pair: half 0) */
+  const bool xprim = !BPAIR<XG, 0> || c.l < 16; /* the lane that counts the second bank's row (pair: half 0) */
   /* XA: the second bank has rows in the wave; without, its terms are exact zeros and its row state is
      not carried through the loop (fewer live registers in the common copy) */
-  if constexpr (XG && XA) g20 += (r.x.ex && r.x.act && xprim) ? r.x.D * r.x.Jv * r.x.Jv : 0.f;
-  if constexpr (YBANK<XG> && XA)
-    g20 += (r.y.ex && r.y.act && (YFLOOR<XG> || c.l < 16)) ? r.y.D * r.y.Jv * r.y.Jv : 0.f;
-  if constexpr (ZPAIR<XG> && XA) g20 += (r.z.ex && r.z.act && c.l < 16) ? r.z.D * r.z.Jv * r.z.Jv : 0.f;
+  if constexpr (XG && XA) g20 += (r.xb[0].ex && r.xb[0].act && xprim) ? r.xb[0].D * r.xb[0].Jv * r.xb[0].Jv : 0.f;
+  if constexpr ((NBANK<XG> > 1) && XA)
+    g20 += (r.xb[1].ex && r.xb[1].act && (!BPAIR<XG, 1> || c.l < 16)) ? r.xb[1].D * r.xb[1].Jv * r.xb[1].Jv : 0.f;
+  if constexpr (BPAIR<XG, 2> && XA)
+    g20 += (r.xb[2].ex && r.xb[2].act && (!BPAIR<XG, 2> || c.l < 16)) ? r.xb[2].D * r.xb[2].Jv * r.xb[2].Jv : 0.f;
   float cc[4] = {isd ? search * (Ma - fs) : 0.f, isd ? search * Mv : 0.f, isd ? search * grad : 0.f, g20};
   if constexpr (ZL) {
 #pragma unroll
@@ -3326,11 +3324,12 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
     DlJ = r.hl ? r.Dl * sv : 0.f;
     DlJ2 = DlJ * sv;
   }
-  const float DXJ = (XG && XA && r.x.ex && xprim) ? r.x.D * r.x.Jv : 0.f, DXJ2 = (XG && XA) ? DXJ * r.x.Jv : 0.f;
-  const float DYJ = (YBANK<XG> && XA && r.y.ex && (YFLOOR<XG> || c.l < 16)) ? r.y.D * r.y.Jv : 0.f,
-              DYJ2 = (YBANK<XG> && XA) ? DYJ * r.y.Jv : 0.f;
-  const float DZJ = (ZPAIR<XG> && XA && r.z.ex && c.l < 16) ? r.z.D * r.z.Jv : 0.f,
-              DZJ2 = (ZPAIR<XG> && XA) ? DZJ * r.z.Jv : 0.f;
+  const float DXJ = (XG && XA && r.xb[0].ex && xprim) ? r.xb[0].D * r.xb[0].Jv : 0.f,
+              DXJ2 = (XG && XA) ? DXJ * r.xb[0].Jv : 0.f;
+  const float DYJ = ((NBANK<XG> > 1) && XA && r.xb[1].ex && (!BPAIR<XG, 1> || c.l < 16)) ? r.xb[1].D * r.xb[1].Jv : 0.f,
+              DYJ2 = ((NBANK<XG> > 1) && XA) ? DYJ * r.xb[1].Jv : 0.f;
+  const float DZJ = (BPAIR<XG, 2> && XA && r.xb[2].ex && c.l < 16) ? r.xb[2].D * r.xb[2].Jv : 0.f,
+              DZJ2 = (BPAIR<XG, 2> && XA) ? DZJ * r.xb[2].Jv : 0.f;
   float d1 = cc[2], d2 = c2 + cc[3];
   if (!(d1 < 0.f) || !(d2 > 0.f)) return 0.f;
   const float gtol = sol_ls_tolerance<DS>(cfg) * (-d1);
@@ -3365,17 +3364,17 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
       }
       if constexpr (XANY) {
         /* second-bank contact row (the copy without it runs while the bank has no row in the wave;
-           a branch on r.x.any here was if-converted as the joint-limit one was) */
-        const float x = r.x.jar + alpha * r.x.Jv;
+           a branch on r.xb[0].any here was if-converted as the joint-limit one was) */
+        const float x = r.xb[0].jar + alpha * r.xb[0].Jv;
         g1 += DXJ * fminf(x, 0.f);
         g2 += x < 0.f ? DXJ2 : 0.f;
-        if constexpr (YBANK<XG>) {
-          const float xy = r.y.jar + alpha * r.y.Jv;
+        if constexpr (NBANK<XG> > 1) {
+          const float xy = r.xb[1].jar + alpha * r.xb[1].Jv;
           g1 += DYJ * fminf(xy, 0.f);
           g2 += xy < 0.f ? DYJ2 : 0.f;
         }
-        if constexpr (ZPAIR<XG>) {
-          const float xz = r.z.jar + alpha * r.z.Jv;
+        if constexpr (BPAIR<XG, 2>) {
+          const float xz = r.xb[2].jar + alpha * r.xb[2].Jv;
           g1 += DZJ * fminf(xz, 0.f);
           g2 += xz < 0.f ? DZJ2 : 0.f;
         }
@@ -3419,24 +3418,25 @@ __device__ __forceinline__ float hmul_pair(const Ctx& c, const Rows& r, const fl
   const float cs0 = colsum16_pre(jr, w0);
   const float cs1 = colsum16((const gfloat_t*)pair_jrows<XG>(c.L) + c.l * CAP, wp);
   const float so = tsh(cs0, ddep), sx = tsh(cs0, 16 + ddep), s2 = tsh(cs1, ddep), s3 = tsh(cs1, 16 + ddep);
+  /* the floor banks: per bank, written out */
   float s4 = 0.f, s5 = 0.f;
   if constexpr (XFLOOR<XG>) {
     /* XG 4, 6: the floor colliders' bank is part of H_t */
-    if (r.x.any) {
-      const float jf = row_dot_x(c, r, V_TMP);
-      const float wf = (r.x.ex && r.x.act) ? r.x.D * jf : 0.f;
+    if (r.xb[0].any) {
+      const float jf = row_dot_bank<0>(c, r, V_TMP);
+      const float wf = (r.xb[0].ex && r.xb[0].act) ? r.xb[0].D * jf : 0.f;
       const float cs2 = colsum16((const gfloat_t*)xrows(c.L) + c.l * CAP, wf);
       s4 = tsh(cs2, ddep);
       s5 = tsh(cs2, 16 + ddep);
     }
   }
   float s6 = 0.f, s7 = 0.f;
-  if constexpr (YFLOOR<XG>) {
+  if constexpr (BFLOOR<XG, 1>) {
     /* XG 6: and the second floor bank */
-    if (r.y.any) {
-      const float jf = row_dot_y(c, r, V_TMP);
-      const float wf = (r.y.ex && r.y.act) ? r.y.D * jf : 0.f;
-      const float cs3 = colsum16((const gfloat_t*)yrows(c.L) + c.l * CAP, wf);
+    if (r.xb[1].any) {
+      const float jf = row_dot_bank<1>(c, r, V_TMP);
+      const float wf = (r.xb[1].ex && r.xb[1].act) ? r.xb[1].D * jf : 0.f;
+      const float cs3 = colsum16((const gfloat_t*)bank_rows<1>(c.L) + c.l * CAP, wf);
       s6 = tsh(cs3, ddep);
       s7 = tsh(cs3, 16 + ddep);
     }
@@ -3449,11 +3449,11 @@ __device__ __forceinline__ float hmul_pair(const Ctx& c, const Rows& r, const fl
     const bool f2 = (pb & 1u) != 0u, f3 = (pb & 2u) != 0u;
     y = Mp + (f0 ? so : 0.f) + (f1 ? sx : 0.f) + (f2 ? s2 : 0.f) + (f3 ? s3 : 0.f);
     if constexpr (XFLOOR<XG>) {
-      const bool f4 = (r.x.rowmask & 0xFFFFu) != 0u, f5 = (r.x.rowmask >> 16) != 0u;
+      const bool f4 = (r.xb[0].rowmask & 0xFFFFu) != 0u, f5 = (r.xb[0].rowmask >> 16) != 0u;
       y += (f4 ? s4 : 0.f) + (f5 ? s5 : 0.f);
     }
-    if constexpr (YFLOOR<XG>) {
-      const bool f6 = (r.y.rowmask & 0xFFFFu) != 0u, f7 = (r.y.rowmask >> 16) != 0u;
+    if constexpr (BFLOOR<XG, 1>) {
+      const bool f6 = (r.xb[1].rowmask & 0xFFFFu) != 0u, f7 = (r.xb[1].rowmask >> 16) != 0u;
       y += (f6 ? s6 : 0.f) + (f7 ? s7 : 0.f);
     }
     if (r.hf && r.actf) y += r.Df * p;
@@ -3518,39 +3518,40 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
   float Ma = mul_m_dot(c, r, jr, x, V_TMP, jw, V_TMP2, js);
   jw -= r.aref;
   js -= r.aref;
+  /* per bank, written out (the warm start, and the step's jar += alpha Jv below) */
   float jwx = 0.f, jsx = 0.f;
-  if (XG && XA && r.x.any) {
-    jwx = row_dot_x(c, r, V_TMP);
-    jsx = row_dot_x(c, r, V_TMP2);
-    if constexpr (XPAIR<XG>) {
+  if (XG && XA && r.xb[0].any) {
+    jwx = row_dot_bank<0>(c, r, V_TMP);
+    jsx = row_dot_bank<0>(c, r, V_TMP2);
+    if constexpr (BPAIR<XG, 0>) {
       jwx += xor16f(jwx);
       jsx += xor16f(jsx);
     }
-    jwx -= r.x.aref;
-    jsx -= r.x.aref;
+    jwx -= r.xb[0].aref;
+    jsx -= r.xb[0].aref;
   }
   float jwy = 0.f, jsy = 0.f;
-  if constexpr (YBANK<XG> && XA) {
-    if (r.y.any) {
-      jwy = row_dot_y(c, r, V_TMP);
-      jsy = row_dot_y(c, r, V_TMP2);
-      if constexpr (YPAIR<XG>) {
+  if constexpr ((NBANK<XG> > 1) && XA) {
+    if (r.xb[1].any) {
+      jwy = row_dot_bank<1>(c, r, V_TMP);
+      jsy = row_dot_bank<1>(c, r, V_TMP2);
+      if constexpr (BPAIR<XG, 1>) {
         jwy += xor16f(jwy);
         jsy += xor16f(jsy);
       }
-      jwy -= r.y.aref;
-      jsy -= r.y.aref;
+      jwy -= r.xb[1].aref;
+      jsy -= r.xb[1].aref;
     }
   }
   float jwz = 0.f, jsz = 0.f;
-  if constexpr (ZPAIR<XG> && XA) {
-    if (r.z.any) {
-      jwz = row_dot_z(c, r, V_TMP);
-      jsz = row_dot_z(c, r, V_TMP2);
+  if constexpr (BPAIR<XG, 2> && XA) {
+    if (r.xb[2].any) {
+      jwz = row_dot_bank<2>(c, r, V_TMP);
+      jsz = row_dot_bank<2>(c, r, V_TMP2);
       jwz += xor16f(jwz); /* the pair's row: both halves */
       jsz += xor16f(jsz);
-      jwz -= r.z.aref;
-      jsz -= r.z.aref;
+      jwz -= r.xb[2].aref;
+      jsz -= r.xb[2].aref;
     }
   }
   tsync();
@@ -3562,14 +3563,14 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     x = qs;
     Ma = mul_m(c, x, V_TMP);
     r.jar = js;
-    r.x.jar = jsx;
-    r.y.jar = jsy;
-    if constexpr (ZPAIR<XG>) r.z.jar = jsz;
+    r.xb[0].jar = jsx;
+    r.xb[1].jar = jsy;
+    if constexpr (BPAIR<XG, 2>) r.xb[2].jar = jsz;
   } else {
     r.jar = jw;
-    r.x.jar = jwx;
-    r.y.jar = jwy;
-    if constexpr (ZPAIR<XG>) r.z.jar = jwz;
+    r.xb[0].jar = jwx;
+    r.xb[1].jar = jwy;
+    if constexpr (BPAIR<XG, 2>) r.xb[2].jar = jwz;
   }
   STAMP(S_WARM);
   r.jf = x - r.af;
@@ -3594,21 +3595,21 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     x += alpha * search;
     Ma += alpha * Mv;
     r.jar += alpha * r.Jv;
-    if constexpr (XG && XA) r.x.jar += alpha * r.x.Jv;
-    if constexpr (YBANK<XG> && XA) r.y.jar += alpha * r.y.Jv;
-    if constexpr (ZPAIR<XG> && XA) r.z.jar += alpha * r.z.Jv;
+    if constexpr (XG && XA) r.xb[0].jar += alpha * r.xb[0].Jv;
+    if constexpr ((NBANK<XG> > 1) && XA) r.xb[1].jar += alpha * r.xb[1].Jv;
+    if constexpr (BPAIR<XG, 2> && XA) r.xb[2].jar += alpha * r.xb[2].Jv;
     r.jf += alpha * search;
     if (r.anyl) r.jl += alpha * (r.sl * search);
     float oldcost = cost;
-    const int pa = r.act, pf = r.actf, plo = r.actl, pa2 = (XG && XA) ? r.x.act : 0,
-              pa3 = (YFLOOR<XG> && XA) ? r.y.act : 0;
+    const int pa = r.act, pf = r.actf, plo = r.actl, pa2 = (XG && XA) ? r.xb[0].act : 0,
+              pa3 = (BFLOOR<XG, 1> && XA) ? r.xb[1].act : 0;
     /* the iteration's three team sums in one interleaved reduction (the same DPP sequence per
        value, so the bits of separate tsum calls): cost, |grad|^2 and the active-set change */
     float red[3];
     red[0] = update_constraint_lane<XG, XA>(c, r, jr, x, qs, fs, Ma, grad);
     red[1] = c.l < NV ? grad * grad : 0.f;
-    red[2] = (r.act != pa || r.actf != pf || (XFLOOR<XG> && XA && r.x.act != pa2) ||
-              (YFLOOR<XG> && XA && r.y.act != pa3)) ? 1.f : 0.f;
+    red[2] = (r.act != pa || r.actf != pf || (XFLOOR<XG> && XA && r.xb[0].act != pa2) ||
+              (BFLOOR<XG, 1> && XA && r.xb[1].act != pa3)) ? 1.f : 0.f;
     if (r.anyl && r.actl != plo) red[2] = 1.f;
     tsum_n<3>(red);
     cost = red[0];
@@ -3666,39 +3667,40 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   float Ma = mul_m_dot<FOLD>(c, r, jr, x, V_TMP, jw, V_TMP2, js);
   jw -= r.aref;
   js -= r.aref;
+  /* per bank, written out (the warm start, and the step's jar += alpha Jv below) */
   float jwx = 0.f, jsx = 0.f;
-  if (XG && XA && r.x.any) {
-    jwx = row_dot_x(c, r, V_TMP);
-    jsx = row_dot_x(c, r, V_TMP2);
-    if constexpr (XPAIR<XG>) {
+  if (XG && XA && r.xb[0].any) {
+    jwx = row_dot_bank<0>(c, r, V_TMP);
+    jsx = row_dot_bank<0>(c, r, V_TMP2);
+    if constexpr (BPAIR<XG, 0>) {
       jwx += xor16f(jwx);
       jsx += xor16f(jsx);
     }
-    jwx -= r.x.aref;
-    jsx -= r.x.aref;
+    jwx -= r.xb[0].aref;
+    jsx -= r.xb[0].aref;
   }
   float jwy = 0.f, jsy = 0.f;
-  if constexpr (YBANK<XG> && XA) {
-    if (r.y.any) {
-      jwy = row_dot_y(c, r, V_TMP);
-      jsy = row_dot_y(c, r, V_TMP2);
-      if constexpr (YPAIR<XG>) {
+  if constexpr ((NBANK<XG> > 1) && XA) {
+    if (r.xb[1].any) {
+      jwy = row_dot_bank<1>(c, r, V_TMP);
+      jsy = row_dot_bank<1>(c, r, V_TMP2);
+      if constexpr (BPAIR<XG, 1>) {
         jwy += xor16f(jwy);
         jsy += xor16f(jsy);
       }
-      jwy -= r.y.aref;
-      jsy -= r.y.aref;
+      jwy -= r.xb[1].aref;
+      jsy -= r.xb[1].aref;
     }
   }
   float jwz = 0.f, jsz = 0.f;
-  if constexpr (ZPAIR<XG> && XA) {
-    if (r.z.any) {
-      jwz = row_dot_z(c, r, V_TMP);
-      jsz = row_dot_z(c, r, V_TMP2);
+  if constexpr (BPAIR<XG, 2> && XA) {
+    if (r.xb[2].any) {
+      jwz = row_dot_bank<2>(c, r, V_TMP);
+      jsz = row_dot_bank<2>(c, r, V_TMP2);
       jwz += xor16f(jwz); /* the pair's row: both halves */
       jsz += xor16f(jsz);
-      jwz -= r.z.aref;
-      jsz -= r.z.aref;
+      jwz -= r.xb[2].aref;
+      jsz -= r.xb[2].aref;
     }
   }
   tsync();
@@ -3709,14 +3711,14 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     x = qs;
     Ma = mul_m<FOLD>(c, x, V_TMP);
     r.jar = js;
-    r.x.jar = jsx;
-    r.y.jar = jsy;
-    if constexpr (ZPAIR<XG>) r.z.jar = jsz;
+    r.xb[0].jar = jsx;
+    r.xb[1].jar = jsy;
+    if constexpr (BPAIR<XG, 2>) r.xb[2].jar = jsz;
   } else {
     r.jar = jw;
-    r.x.jar = jwx;
-    r.y.jar = jwy;
-    if constexpr (ZPAIR<XG>) r.z.jar = jwz;
+    r.xb[0].jar = jwx;
+    r.xb[1].jar = jwy;
+    if constexpr (BPAIR<XG, 2>) r.xb[2].jar = jwz;
   }
   STAMP(S_WARM);
   r.jf = x - r.af;
@@ -3756,9 +3758,9 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     }
     Ma += alpha * Mv;
     r.jar += alpha * r.Jv;
-    if constexpr (XG && XA) r.x.jar += alpha * r.x.Jv;
-    if constexpr (YBANK<XG> && XA) r.y.jar += alpha * r.y.Jv;
-    if constexpr (ZPAIR<XG> && XA) r.z.jar += alpha * r.z.Jv;
+    if constexpr (XG && XA) r.xb[0].jar += alpha * r.xb[0].Jv;
+    if constexpr ((NBANK<XG> > 1) && XA) r.xb[1].jar += alpha * r.xb[1].Jv;
+    if constexpr (BPAIR<XG, 2> && XA) r.xb[2].jar += alpha * r.xb[2].Jv;
     r.jf = __builtin_fmaf(alpha, search, r.jf);
     if (r.anyl) r.jl += alpha * (r.sl * search);
     const float oldcost = cost, gold = grad, mgold = mg;
@@ -3890,8 +3892,9 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   /* constraints */
   make_constraints<XG>(c, s, ls, B, cm, r);
   STAMP(S_CON);
-  int nrows = tmaxi(r.nrow + (XG ? r.x.nrow : 0) + (YBANK<XG> ? r.y.nrow : 0) + (ZPAIR<XG> ? r.z.nrow : 0) +
-                     (r.hf || r.hl ? 1 : 0));
+  int nbrow = r.nrow;
+  for_banks<XG>([&](auto b) { nbrow += r.xb[decltype(b)::value].nrow; });
+  int nrows = tmaxi(nbrow + (r.hf || r.hl ? 1 : 0));
   float qacc;
   /* entered by the whole wave when either env has rows (the full Hessian
      build runs on the matrix cores and needs every lane); an env without
@@ -3902,14 +3905,15 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
     int it2 = 0;
     float ft = 0.f;
     /* XG: the solver in two copies, with and without the second bank's terms (wave-uniform
-       r.x.any; branches on it inside the loops were if-converted into every evaluation) */
+       r.xb[0].any; branches on it inside the loops were if-converted into every evaluation) */
     auto solve = [&](auto xa) -> float {
       constexpr bool XA = decltype(xa)::value;
       return SOLVER == ZB_SOLVER_CG
                  ? solve_cg<XG, XA, FOLD, GN, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
                  : solve_newton<XG, XA, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
     };
-    const bool xa = XG != 0 && (r.x.any || (YBANK<XG> && r.y.any) || (ZPAIR<XG> && r.z.any)); /* wave-uniform */
+    bool xa = false; /* wave-uniform: an extra bank has rows */
+    for_banks<XG>([&](auto b) { xa = xa || r.xb[decltype(b)::value].any; });
     const float qn = xa ? solve(BoolC<true>{}) : solve(BoolC<false>{});
     if (nrows > 0) {
       qacc = qn;
@@ -3927,7 +3931,7 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   float fext[6] = {0, 0, 0, 0, 0, 0};
   float cpos[3], cdir[3], cmu;
   (void)contact_point<XG>(c, s, B, 0, cpos, cdir, cmu);
-  float xpos[3], xdir[3], ypos[3], ydir[3];
+  float xpos[3], xdir[3], ypos[3], ydir[3]; /* per bank, written out (and the geom loop below) */
   /* the pair's row direction n +- mu t; the half on geom1's limb (lanes 16-31) takes -F */
   auto pair_dir = [&](float* pos, float* dir) {
     float n[3], t1[3], t2[3];
@@ -3938,31 +3942,31 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
 #pragma unroll
     for (int k = 0; k < 3; k++) dir[k] = hs * (n[k] + sg * (edge < 2 ? t1[k] : t2[k]));
   };
-  if constexpr (XPAIR<XG>) {
-    if (r.x.any) pair_dir(xpos, xdir);
-  } else if (XG && r.x.any) {
+  if constexpr (BPAIR<XG, 0>) {
+    if (r.xb[0].any) pair_dir(xpos, xdir);
+  } else if (XG && r.xb[0].any) {
     (void)contact_point<XG>(c, s, B, 1, xpos, xdir, cmu);
   }
-  if constexpr (YPAIR<XG>) {
-    if (r.y.any) pair_dir(ypos, ydir);
-  } else if (YFLOOR<XG> && r.y.any) {
+  if constexpr (BPAIR<XG, 1>) {
+    if (r.xb[1].any) pair_dir(ypos, ydir);
+  } else if (BFLOOR<XG, 1> && r.xb[1].any) {
     (void)contact_point<XG>(c, s, B, 2, ypos, ydir, cmu);
   }
   float zpos[3], zdir[3];
-  if constexpr (ZPAIR<XG>) {
-    if (r.z.any) pair_dir(zpos, zdir);
+  if constexpr (BPAIR<XG, 2>) {
+    if (r.xb[2].any) pair_dir(zpos, zdir);
   }
   const int rgeom = c.l >> 4;
   float tch0 = 0.f, tch1 = 0.f;
-  for (int g = 0; g < (ZPAIR<XG> ? 4 * NGEOM : YBANK<XG> ? 3 * NGEOM : XG ? 2 * NGEOM : NGEOM); g++) {
+  for (int g = 0; g < (BPAIR<XG, 2> ? 4 * NGEOM : (NBANK<XG> > 1) ? 3 * NGEOM : XG ? 2 * NGEOM : NGEOM); g++) {
     /* geom g: bank g / 2, lanes 16 (g % 2) .. + 15 (XG 4: bank 2, XG 6: bank 3 = the pair's halves) */
-    const bool b1 = XG && g >= NGEOM && g < 2 * NGEOM, b2 = YBANK<XG> && g >= 2 * NGEOM && g < 3 * NGEOM,
-               b3 = ZPAIR<XG> && g >= 3 * NGEOM;
-    if (b1 && !r.x.any) continue; /* wave-uniform */
-    if (b2 && !r.y.any) continue;
-    if (b3 && !r.z.any) continue;
-    const bool mine = (b3 ? r.z.ex : b2 ? r.y.ex : b1 ? r.x.ex : r.ex) && rgeom == (g & 1);
-    const float rf = b3 ? r.z.f : b2 ? r.y.f : b1 ? r.x.f : r.f;
+    const bool b1 = XG && g >= NGEOM && g < 2 * NGEOM, b2 = (NBANK<XG> > 1) && g >= 2 * NGEOM && g < 3 * NGEOM,
+               b3 = BPAIR<XG, 2> && g >= 3 * NGEOM;
+    if (b1 && !r.xb[0].any) continue; /* wave-uniform */
+    if (b2 && !r.xb[1].any) continue;
+    if (b3 && !r.xb[2].any) continue;
+    const bool mine = (b3 ? r.xb[2].ex : b2 ? r.xb[1].ex : b1 ? r.xb[0].ex : r.ex) && rgeom == (g & 1);
+    const float rf = b3 ? r.xb[2].f : b2 ? r.xb[1].f : b1 ? r.xb[0].f : r.f;
     const float* pp = b3 ? zpos : b2 ? ypos : b1 ? xpos : cpos;
     const float* dd = b3 ? zdir : b2 ? ydir : b1 ? xdir : cdir;
     float F[3] = {0, 0, 0}, tq[3] = {0, 0, 0};
@@ -3980,9 +3984,9 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
     /* the pair's halves: g = 2 geom2's body (+F), g = 3 geom1's (-F, in xdir); each foot's touch
        sensor takes the pair's normal force (its geom is in the contact) */
     const int gg = b3 ? m->pair_geom[g == 3 * NGEOM ? 1 : 0]
-                   : (YFLOOR<XG> && b2) ? c.L->ysel[g - 2 * NGEOM]
+                   : (BFLOOR<XG, 1> && b2) ? c.L->ysel[g - 2 * NGEOM]
                    : b2 ? m->pair_geom[g == 2 * NGEOM ? 1 : 0]
-                   : (XPAIR<XG> && b1) ? m->pair_geom[g == NGEOM ? 1 : 0]
+                   : (BPAIR<XG, 0> && b1) ? m->pair_geom[g == NGEOM ? 1 : 0]
                    : (XFLOOR<XG> && b1) ? c.L->s.xsel[g - NGEOM] : g;
     if (gg >= 0 && gg < m->ngeom && c.l == m->geom_body[gg]) {
 #pragma unroll
@@ -4935,13 +4939,16 @@ __global__ __launch_bounds__(64) void debug_forward_kernel(StepArgs a) {
     for (int k = 0; k < 10; k++) d[ZB_DBG_CINERT + 10 * l + k] = c.L->ci[l][k];
     for (int k = 0; k < 6; k++) d[ZB_DBG_CVEL + 6 * l + k] = B.cv[k];
   }
-  int nefc = (int)tsum((float)((r.ex ? 1 : 0) + (XG && r.x.ex && (!XPAIR<XG> || l < 16) ? 1 : 0) +
-                               (YBANK<XG> && r.y.ex && (YFLOOR<XG> || l < 16) ? 1 : 0) +
-                               (ZPAIR<XG> && r.z.ex && l < 16 ? 1 : 0) + (r.hf ? 1 : 0) +
+  /* per bank, written out */
+  int nefc = (int)tsum((float)((r.ex ? 1 : 0) + (XG && r.xb[0].ex && (!BPAIR<XG, 0> || l < 16) ? 1 : 0) +
+                               ((NBANK<XG> > 1) && r.xb[1].ex && (!BPAIR<XG, 1> || l < 16) ? 1 : 0) +
+                               (BPAIR<XG, 2> && r.xb[2].ex && l < 16 ? 1 : 0) + (r.hf ? 1 : 0) +
                                (r.hl ? 1 : 0)));
   if (l == 0) {
     d[ZB_DBG_MISC + 0] = (float)nefc;
-    d[ZB_DBG_MISC + 1] = (float)((r.nrow + (XG ? r.x.nrow / (XPAIR<XG> ? 2 : 1) : 0) + (YBANK<XG> ? r.y.nrow / (YPAIR<XG> ? 2 : 1) : 0) + (ZPAIR<XG> ? r.z.nrow / 2 : 0)) / 4);
+    d[ZB_DBG_MISC + 1] = (float)((r.nrow + (XG ? r.xb[0].nrow / (BPAIR<XG, 0> ? 2 : 1) : 0) +
+                                  ((NBANK<XG> > 1) ? r.xb[1].nrow / (BPAIR<XG, 1> ? 2 : 1) : 0) +
+                                  (BPAIR<XG, 2> ? r.xb[2].nrow / 2 : 0)) / 4);
     d[ZB_DBG_MISC + 2] = sen.touch[0];
     d[ZB_DBG_MISC + 3] = sen.touch[1];
     for (int k = 0; k < 4; k++) d[ZB_DBG_MISC + 4 + k] = sen.fq[k];

@@ -18,7 +18,7 @@ Regenerating: when a change alters the engine's rounding on purpose, check it ag
 oracle-based tests first (tests/test_gpu_parity.py, tests/test_gpu_colliders.py), then run this
 script on the GPU at that commit and commit the new files together with the change; main() refuses
 to write a case that lost what makes it worth having (an episode end, a solve below the iteration
-cap, second-bank rows).
+cap, second-bank rows, a contact in every extra contact-row bank of the case's kernel: bank_envs).
 """
 
 import argparse
@@ -51,7 +51,21 @@ CASES = {
     "cg_many": dict(steps=8, seed=26, model="zbot_like_many.xml", start="touching"),
     # (f) the sole pair, from states with the soles crossed
     "cg_sole_pair": dict(steps=8, seed=27, model="sole_pair", start="crossing"),
+    # (g) the kernels no case above runs: the cylinder / ellipsoid rules (XG 2), the pair beside one
+    # and two floor banks (XG 4, 6), the nine colliders with the unfolded solve_cg masks, and Newton
+    # (hessian_factor, hsolve_pair) with every kind of extra bank. The pair models lie or stand on
+    # the floor with the soles crossed. check_case counts, per extra bank, the envs that fill it
+    "cg_cyl": dict(steps=8, seed=28, model="zbot_like_cyl.xml", start="touching"),
+    "cg_limbs_pair": dict(steps=8, seed=29, model="limbs_pair", start="crossing_touching"),
+    "cg_many_pair": dict(steps=8, seed=30, model="many_pair", start="crossing_touching"),
+    "cg_many_eulerdamp": dict(steps=8, seed=31, model="zbot_like_many.xml", start="touching", eulerdamp=True),
+    "newton_limbs": dict(steps=8, seed=32, solver="newton", model="zbot_like_limbs.xml", start="touching"),
+    "newton_many": dict(steps=8, seed=33, solver="newton", model="zbot_like_many.xml", start="touching"),
+    "newton_sole_pair": dict(steps=8, seed=34, solver="newton", model="sole_pair", start="crossing_touching"),
+    "newton_many_pair": dict(steps=8, seed=35, solver="newton", model="many_pair", start="crossing_touching"),
 }
+# the cases recorded before the per-bank count existed: their fixtures stay, check_case only prints it
+BANKS_PRINTED_ONLY = ("cg_limbs", "cg_many", "cg_sole_pair")
 
 
 def case_model(model=None):
@@ -59,10 +73,10 @@ def case_model(model=None):
 
     if model is None:
         return compile_model()
-    if model == "sole_pair":
+    if model in ("sole_pair", "limbs_pair", "many_pair"):
         import collider_util as U  # noqa: PLC0415
 
-        return compile_model(U.sole_pair_desc())
+        return compile_model(getattr(U, model + "_desc")())
     from zbot_amd.mjcf import load_mjcf  # noqa: PLC0415
 
     return compile_model(load_mjcf(os.path.join(ROOT, "ksim-gym-zbot_amd", "assets", model)))
@@ -88,6 +102,8 @@ def start_qpos(cm, start, seed):
 
     if start == "touching":
         return U.touching_states(cm, N, seed).astype(np.float32)
+    if start == "crossing_touching":
+        return U.crossing_touching_states(cm, N, seed).astype(np.float32)
     return U.crossing_states(cm, N, seed, air=False).astype(np.float32)
 
 
@@ -96,6 +112,36 @@ def second_bank_envs(cm, qpos) -> int:
     import collider_util as U  # noqa: PLC0415
 
     return sum(any(len(cons) > 0 for cons in U.contacts(cm, q.astype(np.float64))[2:]) for q in qpos)
+
+
+def bank_envs(cm, cfg, qpos) -> list[tuple[str, int]]:
+    """Per extra contact-row bank of the model's kernel, in bank order: what it holds and how many
+    envs' start states put a contact into it. A floor bank takes two of the colliders beyond the
+    soles within reach of the floor, in geom order (collider_util.bank2_candidates; a model with at
+    most two such colliders has one floor bank, any other two), and is filled by a floor contact on
+    one of its two (collider_util.contacts); the sole pair has the bank after the floor banks, filled
+    when the oracle's constraint rows hold a contact row without root columns (the pair's only).
+    The oracle is the repository's own CPU one (oracle/oracle.py, its libraries built by
+    __graft_entry__.build() or on first use by oracle.build()); nothing outside the tree is read."""
+    import collider_util as U  # noqa: PLC0415
+
+    m = cm.cmodel
+    q64 = [q.astype(np.float64) for q in qpos]
+    out = []
+    if m.ngeom > 2:
+        cand = [U.bank2_candidates(cm, q) for q in q64]
+        con = [U.contacts(cm, q, margin=float(m.floor_margin)) for q in q64]
+        for b in range(1 if m.ngeom <= 4 else 2):
+            out.append((f"floor bank {b + 1}", sum(any(len(con[e][g]) > 0 for g in cand[e][2 * b:2 * b + 2])
+                                                   for e in range(len(q64)))))
+    if m.npair:
+        sys.path.insert(0, os.path.join(ROOT, "oracle"))
+        import oracle as O  # noqa: PLC0415
+
+        O.build()
+        rows = [O.constraint_problem(m, cfg, q, np.zeros(26, np.float32), precision="f64") for q in qpos]
+        out.append(("sole pair", sum(bool(((p["type"] == 2) & (np.abs(p["J"][:, :6]).max(1) == 0)).any()) for p in rows)))
+    return out
 
 
 def run_engine(cm, cfg, n, seed, actions, qpos):
@@ -163,6 +209,11 @@ def check_case(name, data, cm, cfg, qpos) -> None:
         nb = second_bank_envs(cm, qpos)
         print(f"  {name}: {nb} of {N} envs start with second-bank rows")
         assert nb >= 1, f"{name}: no env has rows in the second bank"
+    if kw.get("start") is not None:
+        banks = bank_envs(cm, cfg, qpos)
+        print(f"  {name}: envs that start with a contact in " + ", ".join(f"{what}: {k} of {N}" for what, k in banks))
+        if name not in BANKS_PRINTED_ONLY:
+            assert all(k >= 1 for _, k in banks), f"{name}: a bank of its kernel stays empty ({banks})"
 
 
 def main():

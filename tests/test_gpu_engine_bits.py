@@ -5,7 +5,8 @@ stored array compared with array_equal: the per-step reward / done / success / s
 the final state and RNG rows and every output of the last step, for 64 envs and for the first
 three envs alone. The cases cover the CG and Newton kernels of the default model, the implicit
 damping, pushes with domain randomization, the second contact-row bank of the limbs and the
-nine-collider model and the sole pair.
+nine-collider model and the sole pair, and every kind of extra bank (one or two floor banks, the
+cylinder / ellipsoid rules, the pair alone and beside them) under both solvers.
 
 A change that is meant to keep every rounding (fewer instructions, another schedule, another
 build flag) passes unchanged. A change that alters rounding on purpose regenerates the fixtures on
