@@ -237,6 +237,42 @@ __device__ __forceinline__ void tsum_n(float v[N]) {
     v[N - 1] = a + b;
   }
 }
+/* One stage of a transposing butterfly, for the two in-row pairings whose side bit is a DPP bank
+   (a bank is four lanes of a 16-lane row): the row mirror (lane ^ 15; side bit 3 = banks 2, 3) and
+   the half-row mirror (lane ^ 7; side bit 2 = banks 1, 3). The select form of a stage,
+       u = (s ? hi : lo) + dpp(s ? lo : hi),
+   gives a lane on side 0 its lo plus its partner's lo and a lane on side 1 its hi plus its partner's
+   hi: two selects and an add per slot. Here the caller has u = lo + dpp(lo) in every lane, and one
+   DPP add of hi whose bank mask writes side 1 only puts hi + dpp(hi) there: two instructions per
+   slot. Each sum has the select form's two operands (fp add commutes), so the bits are the same.
+   The adds of a stage share one asm. The compiler's hazard recognizer neither sees a VALU write
+   inside an asm nor counts its instructions, so the two wait states a DPP read needs after a VALU
+   write of its source are spelled out on both sides: one s_nop before the adds (their sources may
+   have just been written) and one after them (the next stage reads their results through DPP). */
+__device__ __forceinline__ void dpp_hi8_mirror(float u[8], const float h[8]) {
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %8, %8 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %1, %9, %9 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %2, %10, %10 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %3, %11, %11 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %4, %12, %12 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %5, %13, %13 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %6, %14, %14 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %7, %15, %15 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "s_nop 1"
+      : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3]), "+v"(u[4]), "+v"(u[5]), "+v"(u[6]), "+v"(u[7])
+      : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]), "v"(h[4]), "v"(h[5]), "v"(h[6]), "v"(h[7]));
+}
+__device__ __forceinline__ void dpp_hi4_half(float u[4], const float h[4]) {
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %4, %4 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %1, %5, %5 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %2, %6, %6 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %3, %7, %7 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "s_nop 1"
+      : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3])
+      : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
+}
 /* 21 team sums (the root Schur complement), written to out[0..20] in LDS: a
  * transposing butterfly instead of 21 all-lane reductions. Rows 0/1 of the team
  * first exchange halves with v_permlane16_swap (value i stays in row 0, value
@@ -244,6 +280,7 @@ __device__ __forceinline__ void tsum_n(float v[N]) {
  * half of the slots on the lane's side and add the partner's copy of them, so
  * lane 16r + c ends with the full sum of value 11r + c (67 VALU instructions
  * instead of 126). The caller syncs before reading out[]. */
+template <bool MD = false>
 __device__ __forceinline__ void reduce21_to(const float v[21], float* out) {
   float w[16];
 #pragma unroll
@@ -256,12 +293,22 @@ __device__ __forceinline__ void reduce21_to(const float v[21], float* out) {
   for (int i = 11; i < 16; i++) w[i] = 0.f;
   const int li = threadIdx.x & 15;
   float u8[8], u4[4], u2[2];
+  if constexpr (MD) {
+  /* side bits 3 and 2 are DPP banks (dpp_hi8_mirror) */
+#pragma unroll
+  for (int k = 0; k < 8; k++) u8[k] = w[k] + dppf<0x140>(w[k]);
+  dpp_hi8_mirror(u8, w + 8);
+#pragma unroll
+  for (int k = 0; k < 4; k++) u4[k] = u8[k] + dppf<0x141>(u8[k]);
+  dpp_hi4_half(u4, u8 + 4);
+  } else {
   const bool s1 = li >= 8;
 #pragma unroll
   for (int k = 0; k < 8; k++) u8[k] = (s1 ? w[8 + k] : w[k]) + dppf<0x140>(s1 ? w[k] : w[8 + k]);
   const bool s2 = (li & 4) != 0;
 #pragma unroll
   for (int k = 0; k < 4; k++) u4[k] = (s2 ? u8[4 + k] : u8[k]) + dppf<0x141>(s2 ? u8[k] : u8[4 + k]);
+  }
   const bool s3 = (li & 2) != 0;
 #pragma unroll
   for (int k = 0; k < 2; k++) u2[k] = (s3 ? u4[2 + k] : u4[k]) + dppf<0x4E>(s3 ? u4[k] : u4[2 + k]);
@@ -274,16 +321,23 @@ __device__ __forceinline__ void reduce21_to(const float v[21], float* out) {
  * with the row mirror, then three stages that each keep the half of the slots selected by
  * one lane bit: slot = lane & 7), then the two 16-lane rows added. 29 VALU instructions
  * instead of tsum_n<6>'s 42. */
+template <bool MD = false>
 __device__ __forceinline__ float reduce6_lane(const float v[6]) {
   const int li = threadIdx.x & 15;
   float q[8];
 #pragma unroll
   for (int k = 0; k < 6; k++) q[k] = v[k] + dppf<0x140>(v[k]);
   q[6] = q[7] = 0.f;
-  const bool s2 = (li & 4) != 0;
   float u4[4];
+  if constexpr (MD) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) u4[k] = q[k] + dppf<0x141>(q[k]);
+  dpp_hi4_half(u4, q + 4); /* side bit 2 is a DPP bank */
+  } else {
+  const bool s2 = (li & 4) != 0;
 #pragma unroll
   for (int k = 0; k < 4; k++) u4[k] = (s2 ? q[4 + k] : q[k]) + dppf<0x141>(s2 ? q[k] : q[4 + k]);
+  }
   const bool s1 = (li & 2) != 0;
   float u2[2];
 #pragma unroll
@@ -429,7 +483,28 @@ struct IntC {
 
 /* Diagnostic phase stamps (separate build, -DZB_STAMPS): cycles per phase of the
    step, accumulated per env; never compiled into the product library. */
-#ifdef ZB_STAMPS
+#if defined(ZB_STAMPS) && defined(ZB_BLOCKCOUNT)
+/* Executed-count build (-DZB_STAMPS -DZB_BLOCKCOUNT, scripts/exec_counts.py): the stamp slots hold
+   per-env counters of how often the solver's blocks run, and the prologue's and epilogue's cycles;
+   the phase stamps themselves are off. Team lane 0 counts: every branch counted here is
+   team-uniform (taken on team sums). */
+enum { BC_FORWARD, BC_SOLVE, BC_LS, BC_LS_RET0, BC_LS_LIMIT, BC_EVAL, BC_EVAL_WAVE, BC_IT_CAP, BC_IT_TOL, BC_IT_FULL,
+       BC_PROLOGUE_CYC, BC_EPILOGUE_CYC, BC_STEP, NBC };
+static_assert(NBC <= NSTAMP, "counters live in the stamp slots");
+__device__ __forceinline__ void zb_count(EnvL* L, int i, unsigned long long n) {
+  if ((threadIdx.x & (TEAM - 1)) == 0) L->stamp[i] += n;
+}
+__device__ __forceinline__ unsigned long long zb_now() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+#define STAMP(i) ((void)0)
+#define COUNT(i, n) zb_count(c.L, i, n)
+#elif defined(ZB_STAMPS)
+#define COUNT(i, n) ((void)0)
 __device__ __forceinline__ void zb_stamp(EnvL* L, int i) {
   unsigned long long t;
   __builtin_amdgcn_sched_barrier(0);
@@ -443,6 +518,7 @@ __device__ __forceinline__ void zb_stamp(EnvL* L, int i) {
 #define STAMP(i) zb_stamp(c.L, i)
 #else
 #define STAMP(i) ((void)0)
+#define COUNT(i, n) ((void)0)
 #endif
 
 /* ------------------------------- small math -------------------------------- */
@@ -1275,7 +1351,7 @@ __device__ __forceinline__ void root_schur_mfma() {
  * block is a set of team reductions; the root block is eliminated densely in
  * registers. On return the L rows are in LDS L[][] (L(k, anc_e(k))), pivots in
  * Dk[] (root: also 1/D in Di[]); returns 1/D_j. */
-template <bool MFMA_SCHUR>
+template <bool MFMA_SCHUR, bool MD = false>
 __device__ __forceinline__ float factor_ldl(const Ctx& c, float X[CAP], float Xd, const float (*S)[CAP]) {
   const int ddep = vopq(c.ddep);
   EnvL* L = c.L;
@@ -1383,7 +1459,7 @@ __device__ __forceinline__ float factor_ldl(const Ctx& c, float X[CAP], float Xd
 #pragma unroll
         for (int j = 0; j <= i; j++) g[t++] = wi * X[j];
       }
-      reduce21_to(g, &L->vec[V_TMP2][0]);
+      reduce21_to<MD>(g, &L->vec[V_TMP2][0]);
       tsync();
 #pragma unroll
       for (int t2 = 0; t2 < NG; t2++) g[t2] = L->vec[V_TMP2][t2];
@@ -1665,7 +1741,7 @@ __device__ __forceinline__ float solve_ldl(const Ctx& c, float x, float Dinv) {
 
 /* y = M x (M rows in LDS), x in dof lanes; uses vec[slot] */
 /* XS (solve_cg's copies): one select on x instead of one per product of the root sums */
-template <bool XS = false>
+template <bool XS = false, bool MD = false>
 __device__ __forceinline__ float mul_m(const Ctx& c, float x, int slot) {
   EnvL* L = c.L;
   const int j = c.l;
@@ -1693,7 +1769,7 @@ __device__ __forceinline__ float mul_m(const Ctx& c, float x, int slot) {
 #pragma unroll
     for (int i = 0; i < RMAX; i++)
       si[i] = XS ? (i < nroot ? rounded(mrow[i] * xs) : 0.f) : ((ischain && i < nroot) ? mrow[i] * x : 0.f);
-    const float sr = reduce6_lane(si); /* root lane j: sum j */
+    const float sr = reduce6_lane<MD>(si); /* root lane j: sum j */
     if (j < nroot) y += sr;
   }
   tsync();
@@ -1737,7 +1813,7 @@ __device__ __forceinline__ float row_dot_pre(const Ctx& c, const float jr[CAP], 
  * call): the row loads go out with mul_m's ancestor gather instead of after its reduction and
  * exchange point. jr: the lane's contact-row Jacobian, loaded once per solve. Bit-identical to
  * mul_m followed by row_dot. */
-template <bool XS = false>
+template <bool XS = false, bool MD = false>
 __device__ __forceinline__ float mul_m_dot(const Ctx& c, const Rows& r, const float jr[CAP], float x, int slot, float& jv,
                                            int slot2, float& jv2) {
   EnvL* L = c.L;
@@ -1762,7 +1838,7 @@ __device__ __forceinline__ float mul_m_dot(const Ctx& c, const Rows& r, const fl
 #pragma unroll
     for (int i = 0; i < RMAX; i++)
       si[i] = XS ? (i < nroot ? rounded(mrow[i] * xs) : 0.f) : ((ischain && i < nroot) ? mrow[i] * x : 0.f);
-    const float sr = reduce6_lane(si);
+    const float sr = reduce6_lane<MD>(si);
     if (j < nroot) y += sr;
   }
   tsync();
@@ -2900,23 +2976,36 @@ __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc
    xor 2, quad xor 1). At each stage a lane keeps the half of its column sums on its side and adds
    its partner's copy of them, so lane 16 f + e ends with the geom-f sum of column e (45 instead of
    108 VALU instructions). */
+template <bool MD = false>
 __device__ __forceinline__ float colsum16_pre(const float jr[CAP], float fr) {
   float q[16];
   {
+    /* J rows are zero where no contact. MD: rounded(), since the selects of the first stage kept
+       the products out of its adds; without them the compiler contracts each into an fma */
 #pragma unroll
-    for (int e = 0; e < CAP; e++) q[e] = jr[e] * fr; /* J rows are zero where no contact */
+    for (int e = 0; e < CAP; e++) q[e] = MD ? rounded(jr[e] * fr) : jr[e] * fr;
 #pragma unroll
     for (int e = CAP; e < 16; e++) q[e] = 0.f;
   }
   const int li = threadIdx.x & 15;
   float u8[8], u4[4], u2[2];
   {
-    const bool s1 = li >= 8;
+    if constexpr (MD) {
+      /* side bits 3 and 2 are DPP banks (dpp_hi8_mirror) */
 #pragma unroll
-    for (int k = 0; k < 8; k++) u8[k] = (s1 ? q[8 + k] : q[k]) + dppf<0x140>(s1 ? q[k] : q[8 + k]);
-    const bool s2 = (li & 4) != 0;
+      for (int k = 0; k < 8; k++) u8[k] = q[k] + dppf<0x140>(q[k]);
+      dpp_hi8_mirror(u8, q + 8);
 #pragma unroll
-    for (int k = 0; k < 4; k++) u4[k] = (s2 ? u8[4 + k] : u8[k]) + dppf<0x141>(s2 ? u8[k] : u8[4 + k]);
+      for (int k = 0; k < 4; k++) u4[k] = u8[k] + dppf<0x141>(u8[k]);
+      dpp_hi4_half(u4, u8 + 4);
+    } else {
+      const bool s1 = li >= 8;
+#pragma unroll
+      for (int k = 0; k < 8; k++) u8[k] = (s1 ? q[8 + k] : q[k]) + dppf<0x140>(s1 ? q[k] : q[8 + k]);
+      const bool s2 = (li & 4) != 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) u4[k] = (s2 ? u8[4 + k] : u8[k]) + dppf<0x141>(s2 ? u8[k] : u8[4 + k]);
+    }
     const bool s3 = (li & 2) != 0;
 #pragma unroll
     for (int k = 0; k < 2; k++) u2[k] = (s3 ? u4[2 + k] : u4[k]) + dppf<0x4E>(s3 ? u4[k] : u4[2 + k]);
@@ -2939,7 +3028,7 @@ __device__ __forceinline__ float colsum16(JP Jrow, float fr) {
 /* ZL: solve_cg's copies. The caller's qacc, qs, fs and Ma are exact zeros on the lanes past the dofs,
    whose share of the Gauss cost then needs no mask; the Newton kernels keep the masked forms (their
    direction is not shown to be zero there, and their code stays what it was) */
-template <int XG, bool XA = true, bool HS = true, bool ZL = false>
+template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false>
 __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, const float jr[CAP], float qacc,
                                                        float qs, float fs, float Ma, float& grad) {
   const int ddep = vopq(c.ddep);
@@ -3033,7 +3122,7 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     }
   }
   /* J'f per dof: a dof adds the column sum at its depth of every geom whose chain holds it */
-  const float colsum = colsum16_pre(jr, (ZL || r.ex) ? r.f : 0.f); /* ZL: 0 for a row that does not exist (above) */
+  const float colsum = colsum16_pre<MD>(jr, (ZL || r.ex) ? r.f : 0.f); /* ZL: 0 for a row that does not exist (above) */
   const float so = tsh(colsum, ddep), sx = tsh(colsum, 16 + ddep);
   tsync();
   float qc = 0.f;
@@ -3062,10 +3151,10 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
   grad = Ma - fs - qc;
   return cost;
 }
-template <int XG, bool XA = true, bool HS = true, bool ZL = false>
+template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false>
 __device__ __forceinline__ float update_constraint(const Ctx& c, Rows& r, const float jr[CAP], float qacc, float qs,
                                                   float fs, float Ma, float& grad) {
-  return tsum(update_constraint_lane<XG, XA, HS, ZL>(c, r, jr, qacc, qs, fs, Ma, grad));
+  return tsum(update_constraint_lane<XG, XA, HS, ZL, MD>(c, r, jr, qacc, qs, fs, Ma, grad));
 }
 
 /* G_f = sum_{r in foot f} D_r J_r J_r' (depth-indexed 12x12) for both feet of
@@ -3143,7 +3232,7 @@ __device__ __forceinline__ void add_rows(uint32_t tb, JP J, const float* da, int
  * H of the previous build is updated with the rows whose activity changed
  * (+-D_r J_r J_r') -- MuJoCo's Newton also only re-assembles on a change of
  * the active set, and the change is usually a handful of rows. XG: both banks. */
-template <int XG, bool XA = true>
+template <int XG, bool XA = true, bool MD = false>
 __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, bool full, int pa, int pf, int plo,
                                                 int pa2, int pa3) {
   const int ddep = vopq(c.ddep);
@@ -3266,7 +3355,7 @@ __device__ __forceinline__ float hessian_factor(const Ctx& c, const Rows& r, boo
   tsync();
   /* the full build runs with the whole wave (matrix-core Schur complement); a
      refactor inside the Newton loop may run for one team only (team reductions) */
-  return full ? factor_ldl<true>(c, H, Hd, L->Hs) : factor_ldl<false>(c, H, Hd, L->Hs);
+  return full ? factor_ldl<true, MD>(c, H, Hd, L->Hs) : factor_ldl<false, MD>(c, H, Hd, L->Hs);
 }
 
 /* exact line search along `search`; returns alpha (team-uniform) and Mv/Jv.
@@ -3279,7 +3368,7 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   EnvL* L = c.L;
   /* leaves search in vec[V_TMP]; J rows are zero where no contact: no branch around the loads */
   float unused_;
-  Mv = mul_m_dot<ZL>(c, r, jr, search, V_TMP, r.Jv, -1, unused_);
+  Mv = mul_m_dot<ZL, DS>(c, r, jr, search, V_TMP, r.Jv, -1, unused_);
   if constexpr (XA)
     for_banks<XG>([&](auto b) {
       constexpr int K = decltype(b)::value;
@@ -3331,7 +3420,12 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
   const float DZJ = (BPAIR<XG, 2> && XA && r.xb[2].ex && c.l < 16) ? r.xb[2].D * r.xb[2].Jv : 0.f,
               DZJ2 = (BPAIR<XG, 2> && XA) ? DZJ * r.xb[2].Jv : 0.f;
   float d1 = cc[2], d2 = c2 + cc[3];
-  if (!(d1 < 0.f) || !(d2 > 0.f)) return 0.f;
+  COUNT(BC_LS, 1);
+  if (r.anyl) COUNT(BC_LS_LIMIT, 1);
+  if (!(d1 < 0.f) || !(d2 > 0.f)) {
+    COUNT(BC_LS_RET0, 1);
+    return 0.f;
+  }
   const float gtol = sol_ls_tolerance<DS>(cfg) * (-d1);
   /* the iteration loop in two copies, with and without the joint-limit row (LIM): a branch on
      r.anyl inside the evaluation is if-converted by the compiler into selects around the row's
@@ -3386,14 +3480,31 @@ __device__ __forceinline__ float line_search(const Ctx& c, Rows& r, const float 
     };
     float lo = 0.f, hi = -1.f;
     float alpha = -d1 / d2;
+#ifdef ZB_BLOCKCOUNT
+    int ev = 0;
+#endif
     for (int it = 0; it < sol_ls_iterations<DS>(cfg); it++) {
       eval(alpha, d1, d2);
+#ifdef ZB_BLOCKCOUNT
+      ev++;
+#endif
       if (fabsf(d1) <= gtol) break;
       if (d1 < 0.f) lo = alpha; else hi = alpha;
       float an = alpha - d1 / d2;
       if (!(an > lo) || (hi >= 0.f && !(an < hi))) an = 0.5f * (lo + (hi >= 0.f ? hi : 2.f * alpha));
       alpha = an;
     }
+#ifdef ZB_BLOCKCOUNT
+    {
+      /* the wave runs the larger of its two teams' evaluation counts (a team that is not in this
+         line search counts as 0) */
+      const unsigned long long m = __ballot(true);
+      const int e0 = (m & 1ull) ? __builtin_amdgcn_readlane(ev, 0) : 0;
+      const int e1 = (m >> 32 & 1ull) ? __builtin_amdgcn_readlane(ev, 32) : 0;
+      COUNT(BC_EVAL, (unsigned long long)ev);
+      COUNT(BC_EVAL_WAVE, (unsigned long long)(e0 > e1 ? e0 : e1));
+    }
+#endif
     return alpha;
   };
   /* XA: the caller's instantiation for a wave whose second bank has rows (solve_newton / solve_cg) */
@@ -3515,7 +3626,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
   /* the lane's contact-row Jacobian: constant through the solve, kept in registers */
   float jr[CAP];
   ld_row(&L->u.J[c.l][0], jr);
-  float Ma = mul_m_dot(c, r, jr, x, V_TMP, jw, V_TMP2, js);
+  float Ma = mul_m_dot<false, DS>(c, r, jr, x, V_TMP, jw, V_TMP2, js);
   jw -= r.aref;
   js -= r.aref;
   /* per bank, written out (the warm start, and the step's jar += alpha Jv below) */
@@ -3561,7 +3672,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
   const float cw = cws[0], cs = cws[1];
   if (cw > cs) {
     x = qs;
-    Ma = mul_m(c, x, V_TMP);
+    Ma = mul_m<false, DS>(c, x, V_TMP);
     r.jar = js;
     r.xb[0].jar = jsx;
     r.xb[1].jar = jsy;
@@ -3577,9 +3688,9 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
   r.jl = r.sl * x - r.al;
   float scale = 1.0f / (m->meaninertia * (float)(NV > 1 ? NV : 1));
   float grad;
-  float cost = update_constraint<XG, XA>(c, r, jr, x, qs, fs, Ma, grad);
+  float cost = update_constraint<XG, XA, true, false, DS>(c, r, jr, x, qs, fs, Ma, grad);
   STAMP(S_UPD0);
-  float Dinv = hessian_factor<XG, XA>(c, r, true, 0, 0, 0, 0, 0);
+  float Dinv = hessian_factor<XG, XA, DS>(c, r, true, 0, 0, 0, 0, 0);
   STAMP(S_HESS0);
   float search;
   if constexpr (ANYPAIR<XG> && XA) search = -hsolve_pair<XG>(c, r, jr, grad, Dinv);
@@ -3606,7 +3717,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     /* the iteration's three team sums in one interleaved reduction (the same DPP sequence per
        value, so the bits of separate tsum calls): cost, |grad|^2 and the active-set change */
     float red[3];
-    red[0] = update_constraint_lane<XG, XA>(c, r, jr, x, qs, fs, Ma, grad);
+    red[0] = update_constraint_lane<XG, XA, true, false, DS>(c, r, jr, x, qs, fs, Ma, grad);
     red[1] = c.l < NV ? grad * grad : 0.f;
     red[2] = (r.act != pa || r.actf != pf || (XFLOOR<XG> && XA && r.xb[0].act != pa2) ||
               (BFLOOR<XG, 1> && XA && r.xb[1].act != pa3)) ? 1.f : 0.f;
@@ -3624,7 +3735,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
     /* H depends only on the active set (M, D fixed within a substep):
        refactor only when it changed (MuJoCo's Newton does the same) */
     const bool changed = red[2] > 0.f;
-    if (changed) Dinv = hessian_factor<XG, XA>(c, r, false, pa, pf, plo, pa2, pa3);
+    if (changed) Dinv = hessian_factor<XG, XA, DS>(c, r, false, pa, pf, plo, pa2, pa3);
     STAMP(S_HESS);
     float mg;
     if constexpr (ANYPAIR<XG> && XA) mg = hsolve_pair<XG>(c, r, jr, grad, Dinv);
@@ -3658,13 +3769,14 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   MP m = c.m;
   EnvL* L = c.L;
   __builtin_amdgcn_s_setprio(ZB_SOLVER_PRIO);
+  COUNT(BC_SOLVE, 1);
   float x = w;
   if (c.l < 32) L->vec[V_TMP2][c.l] = qs;
   float jw, js;
   /* the lane's contact-row Jacobian: constant through the solve, kept in registers */
   float jr[CAP];
   ld_row(&L->u.J[c.l][0], jr);
-  float Ma = mul_m_dot<FOLD>(c, r, jr, x, V_TMP, jw, V_TMP2, js);
+  float Ma = mul_m_dot<FOLD, DS>(c, r, jr, x, V_TMP, jw, V_TMP2, js);
   jw -= r.aref;
   js -= r.aref;
   /* per bank, written out (the warm start, and the step's jar += alpha Jv below) */
@@ -3709,7 +3821,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
   tsum_n<2>(cws);
   if (cws[0] > cws[1]) {
     x = qs;
-    Ma = mul_m<FOLD>(c, x, V_TMP);
+    Ma = mul_m<FOLD, DS>(c, x, V_TMP);
     r.jar = js;
     r.xb[0].jar = jsx;
     r.xb[1].jar = jsy;
@@ -3732,7 +3844,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
      integrate's w = qacc with forward's masked qacc), hence x, Ma and the Gauss term; the rows'
      forces are added on dof lanes only (update_constraint_lane's qc), hence grad = Ma - fs - qc,
      mg = M^-1 grad and search = -mg + beta search, and every step keeps x, Ma there. */
-  float cost = update_constraint<XG, XA, false, FOLD>(c, r, jr, x, qs, fs, Ma, grad);
+  float cost = update_constraint<XG, XA, false, FOLD, DS>(c, r, jr, x, qs, fs, Ma, grad);
   STAMP(S_UPD0);
   float mg = solve_pre<GN>(c, grad);
   STAMP(S_SOLVE0);
@@ -3753,6 +3865,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     if (qacc_only && it + 1 == itmax) {
       /* the cap: no further iteration, and the rows' state at the new point (M qacc, the row
          values, forces, active set and gradient) has no reader */
+      COUNT(BC_IT_CAP, 1);
       it++;
       break;
     }
@@ -3764,7 +3877,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     r.jf = __builtin_fmaf(alpha, search, r.jf);
     if (r.anyl) r.jl += alpha * (r.sl * search);
     const float oldcost = cost, gold = grad, mgold = mg;
-    const float cl = update_constraint_lane<XG, XA, false, FOLD>(c, r, jr, x, qs, fs, Ma, grad);
+    const float cl = update_constraint_lane<XG, XA, false, FOLD, DS>(c, r, jr, x, qs, fs, Ma, grad);
     STAMP(S_UPD);
     it++;
     /* MJX's order (solver.py: _update_gradient, then the Polak-Ribiere beta, then the termination
@@ -3786,7 +3899,11 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
       cost = red[0];
       const float improvement = scale * (oldcost - cost);
       const float gradient = scale * sqrtf(red[1]);
-      if (improvement < sol_tolerance<DS>(cfg) || gradient < sol_tolerance<DS>(cfg)) break;
+      if (improvement < sol_tolerance<DS>(cfg) || gradient < sol_tolerance<DS>(cfg)) {
+        COUNT(BC_IT_TOL, 1);
+        break;
+      }
+      COUNT(BC_IT_FULL, 1);
       const float beta = fmaxf(red[2] / fmaxf(red[3], MINVAL), 0.f);
       search = -mg + beta * search;
     } else {
@@ -3858,7 +3975,7 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   /* factor M (copy of rows) */
   float X[CAP];
   float Xd = load_mrow(c, X);
-  float DinvM = factor_ldl<true>(c, X, Xd, L->M);
+  float DinvM = factor_ldl<true, DS>(c, X, Xd, L->M);
   STAMP(S_FACM);
   /* velocities */
   if (c.l < 32) L->vec[V_QVEL][c.l] = c.l < NV ? ls.v : 0.f;
@@ -4687,6 +4804,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const ZbEnvConfig* cfg = a.cfg;
   constexpr bool SD = SMOOTH_DIET<SOLVER, XG, ED != 0>;
   Ctx c;
+#ifdef ZB_BLOCKCOUNT
+  const unsigned long long bc_t0 = zb_now();
+#endif
   make_ctx<SD>(c, m, cfg, a.topo, &g_lds[team], a.seed, (uint32_t)(a.env_offset + ee));
   /* the env's second-bank rows (a team past n: the spare block n) */
   if constexpr (XG) set_xrows(c.L, a.xj + (size_t)(live ? e : a.n_envs) * XJ_STRIDE<XG>);
@@ -4706,6 +4826,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   if (K > 1) load_state<true>(c, s, ls, state_row());
   else load_state<false>(c, s, ls, state_row());
   load_params<SD>(c, s, ls, rand_row());
+#ifdef ZB_BLOCKCOUNT
+  COUNT(BC_PROLOGUE_CYC, zb_now() - bc_t0); /* make_ctx, load_state, load_params */
+#endif
   BodyK B;
   Rows r;
   Sensors& sen = c.L->sen;
@@ -4743,6 +4866,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (!resetting && !ghost) feetech<XG>(c, ls);
       STAMP(S_FEETECH);
       int it_pass = 0;
+      COUNT(BC_FORWARD, 1);
       forward<SOLVER, XG, ED != 0, SD, DS>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
       if (!ghost) iters += it_pass;
       if (!resetting && !ghost) {
@@ -4813,6 +4937,10 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (a.success) a.success[eo] = success ? 1 : 0;
     }
   }
+#ifdef ZB_BLOCKCOUNT
+  const unsigned long long bc_t1 = zb_now();
+  COUNT(BC_STEP, (unsigned long long)nsteps);
+#endif
   if (partial) {
     if (live && c.l == 0) stu_cg((uint32_t*)a.itpart + vopq(e), (uint32_t)iters);
   } else if (live && a.iters && c.l == 0) {
@@ -4848,6 +4976,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
     w[2] = (unsigned long long)__smid();
     w[3] = (unsigned long long)iters;
   }
+#endif
+#ifdef ZB_BLOCKCOUNT
+  COUNT(BC_EPILOGUE_CYC, zb_now() - bc_t1); /* the iteration count, the state store, the chunk hand-off */
 #endif
 #ifdef ZB_STAMPS
   STAMP(S_STEPEND);
