@@ -32,7 +32,7 @@ struct ZbHandle {
   uint64_t seed;
   ZbModel hmodel;
   ZbEnvConfig cfg;
-  ZbModel* dmodel;
+  ZbModel* dmodel; /* the model, and LR_OFFSET bytes on the handle's lane record (zb_host.h) */
   ZbEnvConfig* dcfg;
   int32_t* dtopo; /* [TP_NF][32] per-lane topology */
   float* state;
@@ -114,7 +114,7 @@ int zb_create(const ZbModel* model, const ZbEnvConfig* cfg, int n_envs, int env_
   h->hmodel = *model;
   h->cfg = *cfg;
   size_t n = (size_t)(n_envs > 0 ? n_envs : 1);
-  hipError_t e = hipMalloc(&h->dmodel, sizeof(ZbModel));
+  hipError_t e = hipMalloc(&h->dmodel, zb::LR_OFFSET + zb::LR_FLOATS * sizeof(float));
   if (e == hipSuccess) e = hipMalloc(&h->dcfg, sizeof(ZbEnvConfig));
   if (e == hipSuccess) e = hipMemcpy(h->dcfg, cfg, sizeof(ZbEnvConfig), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc(&h->state, n * ZB_STATE_STRIDE * sizeof(float));
@@ -127,6 +127,11 @@ int zb_create(const ZbModel* model, const ZbEnvConfig* cfg, int n_envs, int env_
     build_topology(model, topo);
     e = hipMalloc(&h->dtopo, sizeof topo);
     if (e == hipSuccess) e = hipMemcpy(h->dtopo, topo, sizeof topo, hipMemcpyHostToDevice);
+    /* the lane record: this model's rows, owned by the handle and never written again */
+    float lrec[zb::LR_FLOATS];
+    zb::build_lane_record(model, topo, lrec);
+    if (e == hipSuccess)
+      e = hipMemcpy(reinterpret_cast<char*>(h->dmodel) + zb::LR_OFFSET, lrec, sizeof lrec, hipMemcpyHostToDevice);
   }
   if (e == hipSuccess) e = hipMemset(h->state, 0, n * ZB_STATE_STRIDE * sizeof(float));
   if (e == hipSuccess) e = hipMemset(h->rnd, 0, n * ZB_RAND_STRIDE * sizeof(float));

@@ -877,6 +877,54 @@ __device__ __forceinline__ float sol_ls_tolerance(CP cfg) {
 template <int SOLVER, int XG, int ED>
 constexpr bool SOL_LITERAL = XG == 0 && ED == 0;
 
+/* ---- the handle's lane record (zb_host.h LR_*; zb_host.cpp build_lane_record) ----
+   The model rows that com_crb_m() and forward()'s actuation read per lane, repacked at zb_create into
+   planes of one 16-byte row per team lane behind the model's device copy (LR_OFFSET), so a part comes
+   in with one global_load_dwordx3 / x4 per plane over 512 contiguous bytes. CR (forward()'s flag): the
+   phases read the record where they read `m->...`, and each part is issued one phase ahead of its
+   reader: com_crb_m's at kinematics' entry, the actuator row at the factorization's. A load hoisted
+   in the source is sunk back to its reader by the compiler, which then waits for it on the spot
+   (DESIGN.md section 10), so the issue point is a volatile asm load, and its wait is written by hand
+   at the reader and tied to the destination registers ("+v"): the compiler's own s_waitcnt insertion
+   does not see an asm load. vmcnt(0) also drains whatever the compiler has in flight, which is always
+   safe. The record is never written after zb_create, so the statements need no memory clobber. The
+   destinations must not be copied or spilled between issue and wait: scripts/phase_waits.py --audit
+   checks that in the ISA. */
+typedef float lr4 __attribute__((ext_vector_type(4)));
+typedef float lr3 __attribute__((ext_vector_type(3)));
+struct LrCrb {
+  lr4 ipos_mass, iquat;
+  lr3 inertia, daxis, dpos;
+};
+struct LrAct {
+  lr3 range_gear; /* act_ctrlrange[a][0], [1], act_gear[a] */
+};
+static_assert(LR_CRB_IPOS_MASS == 0 && LR_CRB_IQUAT == 1 && LR_CRB_INERTIA == 2 && LR_CRB_DAXIS == 3 && LR_CRB_DPOS == 4 &&
+                  LR_PLANE_BYTES == 512, "lr_crb_issue spells the planes' offsets out");
+/* the lane's row in plane `plane` */
+__device__ __forceinline__ const char* lr_row(MP m, int plane) {
+  return reinterpret_cast<const char*>((uint64_t)m) + (LR_OFFSET + (size_t)plane * LR_PLANE_BYTES) +
+         (size_t)(threadIdx.x & (TEAM - 1)) * sizeof(lr4);
+}
+__device__ __forceinline__ void lr_crb_issue(LrCrb& cr, MP m) {
+  const char* p = lr_row(m, LR_CRB);
+  asm volatile("global_load_dwordx4 %0, %5, off\n\t"
+               "global_load_dwordx4 %1, %5, off offset:512\n\t"
+               "global_load_dwordx3 %2, %5, off offset:1024\n\t"
+               "global_load_dwordx3 %3, %5, off offset:1536\n\t"
+               "global_load_dwordx3 %4, %5, off offset:2048"
+               : "=&v"(cr.ipos_mass), "=&v"(cr.iquat), "=&v"(cr.inertia), "=&v"(cr.daxis), "=&v"(cr.dpos)
+               : "v"(p));
+}
+__device__ __forceinline__ void lr_crb_wait(LrCrb& cr) {
+  asm volatile("s_waitcnt vmcnt(0)" : "+v"(cr.ipos_mass), "+v"(cr.iquat), "+v"(cr.inertia), "+v"(cr.daxis), "+v"(cr.dpos));
+}
+__device__ __forceinline__ void lr_act_issue(LrAct& ac, MP m) {
+  const char* p = lr_row(m, LR_ACT);
+  asm volatile("global_load_dwordx3 %0, %1, off" : "=&v"(ac.range_gear) : "v"(p));
+}
+__device__ __forceinline__ void lr_act_wait(LrAct& ac) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(ac.range_gear)); }
+
 /* ancestor dof at depth e of a dof whose limb chain starts at dof `head`
    (root dofs: head < 0): the tree shape makes ancestors dofs 0..NROOT-1
    followed by a contiguous run of the limb (e past the depth: a valid dummy) */
@@ -1116,8 +1164,12 @@ __device__ __forceinline__ void subtree_sum(const Ctx& c, float v[K]) {
 
 /* ------------------------------ mass matrix -------------------------------- */
 /* com, cinert (lane b), cdof (lane j -> LDS), crb, M rows (LDS + return) */
-template <bool SD = false>
-__device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const LaneS& ls, BodyK& B, float cm[3]) {
+/* CR: the inertial rows of the lane's body and the joint rows of the lane's dof come from the lane
+   record's part `lc` (already waited for), which zb_create filled with the rows of the same indices
+   (body l or 0, body dbody or 0) */
+template <bool SD = false, bool CR = false>
+__device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const LaneS& ls, BodyK& B, float cm[3],
+                                          const LrCrb& lc) {
   const int ddep = vopq(c.ddep);
   MP m = c.m;
   EnvL* L = c.L;
@@ -1125,18 +1177,31 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
   const bool isbody = b >= 1 && b < NB;
   const int bb = isbody ? b : 0;
   const float mscale = keepf(c.L->par[P_MSCALE][c.l]);
-  const float bmass = keepf(m->body_mass[bb][0]);
+  float bmass;
+  if constexpr (CR) bmass = keepf(lc.ipos_mass[3]);
+  else bmass = keepf(m->body_mass[bb][0]);
   /* SD: mscale is zero off the bodies (load_params); rounded: the product stays out of the team sum's adds */
   float mass = SD ? rounded(bmass * mscale) : (isbody ? bmass * mscale : 0.f);
   float xipos[3], Ri[9];
   {
-    float ip[3] = {m->body_ipos[isbody ? b : 0][0], m->body_ipos[isbody ? b : 0][1], m->body_ipos[isbody ? b : 0][2]}, t[3];
-    quat_rotate(t, B.xq, ip); /* xmat * ipos */
+    /* the branch without the record is the parent's text, word for word: an equivalent moved registers */
+    float t[3], xi[4];
+    if constexpr (CR) {
+      float ip[3] = {lc.ipos_mass[0], lc.ipos_mass[1], lc.ipos_mass[2]};
+      quat_rotate(t, B.xq, ip); /* xmat * ipos */
 #pragma unroll
-    for (int k = 0; k < 3; k++) xipos[k] = B.xp[k] + t[k];
-    float iq[4] = {m->body_iquat[isbody ? b : 0][0], m->body_iquat[isbody ? b : 0][1],
-                   m->body_iquat[isbody ? b : 0][2], m->body_iquat[isbody ? b : 0][3]}, xi[4];
-    quat_mul(xi, B.xq, iq); /* ximat = frame of xquat * body_iquat (mj_local2Global) */
+      for (int k = 0; k < 3; k++) xipos[k] = B.xp[k] + t[k];
+      float iq[4] = {lc.iquat[0], lc.iquat[1], lc.iquat[2], lc.iquat[3]};
+      quat_mul(xi, B.xq, iq); /* ximat = frame of xquat * body_iquat (mj_local2Global) */
+    } else {
+      float ip[3] = {m->body_ipos[isbody ? b : 0][0], m->body_ipos[isbody ? b : 0][1], m->body_ipos[isbody ? b : 0][2]};
+      quat_rotate(t, B.xq, ip); /* xmat * ipos */
+#pragma unroll
+      for (int k = 0; k < 3; k++) xipos[k] = B.xp[k] + t[k];
+      float iq[4] = {m->body_iquat[isbody ? b : 0][0], m->body_iquat[isbody ? b : 0][1],
+                     m->body_iquat[isbody ? b : 0][2], m->body_iquat[isbody ? b : 0][3]};
+      quat_mul(xi, B.xq, iq); /* ximat = frame of xquat * body_iquat (mj_local2Global) */
+    }
     quat2mat(Ri, xi);
   }
   float ms[4] = {mass, mass * xipos[0], mass * xipos[1], mass * xipos[2]};
@@ -1150,7 +1215,9 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
     float in[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      const float bi = keepf(m->body_inertia[bb][k]);
+      float bi;
+      if constexpr (CR) bi = keepf(lc.inertia[k]);
+      else bi = keepf(m->body_inertia[bb][k]);
       in[k] = SD ? bi * mscale : (isbody ? bi * mscale : 0.f);
     }
     float dif[3] = {xipos[0] - cm[0], xipos[1] - cm[1], xipos[2] - cm[2]};
@@ -1198,8 +1265,13 @@ __device__ __forceinline__ void com_crb_m(const Ctx& c, const EnvS& s, const Lan
       float ja[3], jp[3], t[3], ax[3];
 #pragma unroll
       for (int i = 0; i < 3; i++) {
-        ja[i] = isfree ? (k - 3 == i ? 1.f : 0.f) : m->jnt_axis[bj][i];
-        jp[i] = isfree ? 0.f : m->jnt_pos[bj][i];
+        if constexpr (CR) {
+          ja[i] = isfree ? (k - 3 == i ? 1.f : 0.f) : lc.daxis[i];
+          jp[i] = isfree ? 0.f : lc.dpos[i];
+        } else {
+          ja[i] = isfree ? (k - 3 == i ? 1.f : 0.f) : m->jnt_axis[bj][i];
+          jp[i] = isfree ? 0.f : m->jnt_pos[bj][i];
+        }
       }
       mulmv3(t, R, jp);
       mulmv3(ax, R, ja);
@@ -3961,17 +4033,24 @@ __device__ __forceinline__ void feetech(const Ctx& c, LaneS& ls) {
    VALU diet"): the pointer-jumping schedules from Ctx::pjb / pjd, masks folded into data (the mass
    scale, the cdof rows, lane ZLANE's zeros).
    Bit-identical to the forms they replace, which the other instantiations keep. */
-template <int SOLVER, int XG, bool FQ = true, bool SD = false, bool DS = false>
+/* CR: com_crb_m and the actuation read the handle's lane record instead of the model's arrays, each
+   part issued one phase ahead (lr_crb_issue, lr_act_issue) */
+template <int SOLVER, int XG, bool FQ = true, bool SD = false, bool DS = false, bool CR = false>
 __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, BodyK& B, Rows& r, bool with_sensors,
                                         Sensors& sen, int& iters) {
   MP m = c.m;
   EnvL* L = c.L;
   STAMP(S_ENTRY);
+  LrCrb crb;
+  if constexpr (CR) lr_crb_issue(crb, m);
   kinematics<SD>(c, s, ls, B);
   STAMP(S_KIN);
   float cm[3];
-  com_crb_m<SD>(c, s, ls, B, cm);
+  if constexpr (CR) lr_crb_wait(crb);
+  com_crb_m<SD, CR>(c, s, ls, B, cm, crb);
   STAMP(S_CRB);
+  LrAct lact;
+  if constexpr (CR) lr_act_issue(lact, m);
   /* factor M (copy of rows) */
   float X[CAP];
   float Xd = load_mrow(c, X);
@@ -3988,10 +4067,17 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
   float bias = rne_project<SD>(c, B, ca, zero6);
   /* actuation + passive -> qfrc_smooth, qacc_smooth */
   float act = 0.f;
+  if constexpr (CR) lr_act_wait(lact);
   if (c.act >= 0) {
-    float ct = fminf(fmaxf(ls.ctrl, m->act_ctrlrange[c.act][0]), m->act_ctrlrange[c.act][1]);
-    ls.actforce = m->act_gear[c.act] * ct;
-    act = m->act_gear[c.act] * ls.actforce;
+    if constexpr (CR) {
+      float ct = fminf(fmaxf(ls.ctrl, lact.range_gear[0]), lact.range_gear[1]);
+      ls.actforce = lact.range_gear[2] * ct;
+      act = lact.range_gear[2] * ls.actforce;
+    } else {
+      float ct = fminf(fmaxf(ls.ctrl, m->act_ctrlrange[c.act][0]), m->act_ctrlrange[c.act][1]);
+      ls.actforce = m->act_gear[c.act] * ct;
+      act = m->act_gear[c.act] * ls.actforce;
+    }
   } else {
     ls.actforce = 0.f;
   }
@@ -4748,6 +4834,11 @@ template <int SOLVER, int XG, bool ED>
 constexpr bool SMOOTH_DIET = SOLVER == ZB_SOLVER_CG
                                  ? (XG == 0 || XG == 5 || (XG == 1 && !ED) || (XG == 2 && ED) || (XG == 3 && ED))
                                  : (XG == 0 || XG == 2 || XG == 5);
+/* The step kernels that read the handle's lane record (forward()'s CR): the default-fields copies, where
+   it was measured and the spill table allows it; every other instantiation
+   compiles to the parent's instructions */
+template <int SOLVER, int XG, int ED, bool DS>
+constexpr bool CONST_REC = DS;
 /* DS: the copy for handles whose solver fields are the defaults (sol_iterations; SOL_LITERAL) */
 template <int SOLVER, int XG, int ED, bool DS = false>
 __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
@@ -4803,6 +4894,7 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const ZbModel* m = a.model;
   const ZbEnvConfig* cfg = a.cfg;
   constexpr bool SD = SMOOTH_DIET<SOLVER, XG, ED != 0>;
+  constexpr bool CR = CONST_REC<SOLVER, XG, ED, DS>;
   Ctx c;
 #ifdef ZB_BLOCKCOUNT
   const unsigned long long bc_t0 = zb_now();
@@ -4852,6 +4944,14 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
     if (ch == 0 && (cfg->flags & ZB_F_PUSH)) push_event(c, s, ls, a.curriculum);
     float total = 0.f;
     int ss = ch * cfg->n_substeps / K;
+    /* CR: the substeps left to the end of the control step and of this unit, counted down, so the
+       loop's tests compare with constants: `ss == cfg->n_substeps - 1` below was a vector load of
+       the config and a wait on the spot in every substep */
+    int sleft = 0, sleft_end = 0;
+    if constexpr (CR) {
+      sleft = cfg->n_substeps - ss;
+      sleft_end = cfg->n_substeps - ss_end;
+    }
     bool resetting = false; /* this team re-enters forward() for its reset state */
     bool ghost = false;     /* the other team resets: a discarded forward() pass */
     bool done_reset = false;
@@ -4867,7 +4967,8 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       STAMP(S_FEETECH);
       int it_pass = 0;
       COUNT(BC_FORWARD, 1);
-      forward<SOLVER, XG, ED != 0, SD, DS>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
+      if constexpr (CR) forward<SOLVER, XG, ED != 0, SD, DS, CR>(c, s, ls, B, r, resetting || sleft == 1, sen, it_pass);
+      else forward<SOLVER, XG, ED != 0, SD, DS>(c, s, ls, B, r, resetting || ss == cfg->n_substeps - 1, sen, it_pass);
       if (!ghost) iters += it_pass;
       if (!resetting && !ghost) {
         /* wave-uniform: both teams integrate, or both run the reset / ghost pass */
@@ -4875,7 +4976,13 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
         if constexpr (ED != 0) qacc_e = implicit_damping(c, ls);
         integrate<ED != 0>(c, s, ls, qacc_e);
         STAMP(S_INT);
-        if (++ss < cfg->n_substeps) {
+        if constexpr (CR) {
+          if (--sleft > 0) {
+            if (sleft > sleft_end) continue;
+            partial = true;
+            break;
+          }
+        } else if (++ss < cfg->n_substeps) {
           if (ss < ss_end) continue;
           partial = true; /* wave-uniform: no team resets before the last substep */
           break;

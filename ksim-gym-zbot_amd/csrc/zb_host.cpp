@@ -329,6 +329,32 @@ void build_topology(const ZbModel* m, int32_t t[zb::TP_NF][zb::TOPO_LANES]) {
   }
 }
 
+/* The handle's lane record (zb_host.h LR_*): the model rows com_crb_m() and forward()'s actuation read
+   per team lane, copied into plane-major 16-byte rows. The row indices are the ones the kernel forms
+   (zb_engine.hip: body l or 0 off the bodies; the dof's body from the topology table or 0; the dof's
+   actuator). Copies only: memcpy of whole rows, plain assignments for single values. */
+void build_lane_record(const ZbModel* m, const int32_t t[zb::TP_NF][zb::TOPO_LANES], float rec[zb::LR_FLOATS]) {
+  static_assert(TOPO_LANES == ZB_MAX_BODY, "a body row per lane");
+  const int NB = ZB_NBODY_TASK;
+  memset(rec, 0, sizeof(float) * LR_FLOATS);
+  auto row = [&](int plane, int l) { return rec + (size_t)plane * LR_PLANE_FLOATS + 4 * l; };
+  for (int l = 0; l < TOPO_LANES; l++) {
+    const int bb = (l >= 1 && l < NB) ? l : 0;
+    const int bj = t[TP_DBODY][l] < 0 ? 0 : t[TP_DBODY][l];
+    memcpy(row(LR_CRB + LR_CRB_IPOS_MASS, l), m->body_ipos[bb], 12);
+    row(LR_CRB + LR_CRB_IPOS_MASS, l)[3] = m->body_mass[bb][0];
+    memcpy(row(LR_CRB + LR_CRB_IQUAT, l), m->body_iquat[bb], 16);
+    memcpy(row(LR_CRB + LR_CRB_INERTIA, l), m->body_inertia[bb], 16);
+    memcpy(row(LR_CRB + LR_CRB_DAXIS, l), m->jnt_axis[bj], 16);
+    memcpy(row(LR_CRB + LR_CRB_DPOS, l), m->jnt_pos[bj], 16);
+    const int a = t[TP_ACT][l];
+    if (a >= 0) {
+      memcpy(row(LR_ACT, l), m->act_ctrlrange[a], 8);
+      row(LR_ACT, l)[2] = m->act_gear[a];
+    }
+  }
+}
+
 /* ---- learner (include/zbot_ppo.h "Learner"): argument checks and the host twins' tree ---- */
 
 int check_loss_args(const char* what, const void* const* ptrs, int nptrs, int T, int n, double total,

@@ -27,6 +27,36 @@ constexpr int TOPO_NROOT = 6;  /* root dof chain (the free joint), zb_engine.hip
 constexpr int TOPO_NGEOM = 2;  /* geoms per contact-row bank, zb_engine.hip NGEOM */
 constexpr int TOPO_MAXBD = 8;  /* deepest body, zb_engine.hip MAXBD */
 
+/* The handle's lane record, built once by zb_create (build_lane_record) and read by the step kernels
+   that take it (zb_engine.hip CONST_REC): the model rows that the substep body reads per team lane
+   and waited for on the spot, in the order of the phases that read them. It lies behind the model's
+   device copy, LR_OFFSET bytes from its start, so a kernel needs no pointer of its own for it.
+   Plane-major: plane p holds one 16-byte row per lane, [LR_NPLANE][32][4] fp32, so a wave fetches
+   a plane with one global_load_dwordx3 / x4 over 512 contiguous bytes, and a phase's part (whole
+   planes: 16-byte aligned and padded) with one load per plane. Values are copied, never computed:
+   every bit is the model's. A model never changes after zb_create, so the
+   record is never rebuilt.
+     com_crb_m's part, rows of body bb = l if 1 <= l < nbody, else 0, and of the body of dof l,
+     bj = TP_DBODY[l] if it is >= 0, else 0 (the indices the kernel forms):
+       LR_CRB_IPOS_MASS  body_ipos[bb][0..2], body_mass[bb][0]
+       LR_CRB_IQUAT      body_iquat[bb]     LR_CRB_INERTIA  body_inertia[bb]
+       LR_CRB_DAXIS      jnt_axis[bj]       LR_CRB_DPOS     jnt_pos[bj]
+     the actuation's part, of the actuator a = TP_ACT[l] of dof l (a < 0: a row of zeros, not read):
+       LR_ACT            act_ctrlrange[a][0], act_ctrlrange[a][1], act_gear[a], 0
+   kinematics' rows (body_pos, body_quat, jnt_pos, jnt_axis) are not in it: its loads are covered
+   already (profiles/mem_wait_phases.json). */
+enum {
+  LR_CRB_IPOS_MASS, LR_CRB_IQUAT, LR_CRB_INERTIA, LR_CRB_DAXIS, LR_CRB_DPOS, LR_NCRB,
+  LR_CRB = 0, LR_ACT = LR_NCRB, /* first plane of each part; LR_CRB_* count from LR_CRB */
+  LR_NPLANE = LR_ACT + 1
+};
+constexpr int LR_PLANE_FLOATS = TOPO_LANES * 4;
+constexpr int LR_PLANE_BYTES = LR_PLANE_FLOATS * 4;
+constexpr int LR_FLOATS = LR_NPLANE * LR_PLANE_FLOATS;
+constexpr size_t LR_OFFSET = (sizeof(ZbModel) + 15) / 16 * 16; /* of the record in the model's device buffer */
+/* requires check_model(m) == ZB_OK and t = build_topology(m) */
+void build_lane_record(const ZbModel* m, const int32_t t[TP_NF][TOPO_LANES], float rec[LR_FLOATS]);
+
 /* fail(): record the message for zb_last_error() and return `code` */
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 /* ZB_OK, or ZB_EARG / ZB_EMODEL with the reason in zb_last_error() */

@@ -29,7 +29,7 @@
 namespace zb {
 
 struct StepArgs {
-  const ZbModel* model;     /* device copy */
+  const ZbModel* model;     /* device copy, the handle's lane record behind it (zb_host.h LR_OFFSET) */
   const int32_t* topo;      /* [TP_NF][32] per-lane topology (device) */
   const ZbEnvConfig* cfg;   /* device copy */
   int n_envs;
