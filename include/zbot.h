@@ -32,6 +32,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "zbot_command.h"
 #include "zbot_layout.h"
 #include "zbot_model.h"
 
@@ -195,6 +196,49 @@ int zb_get_solver_iters(ZbHandle* h, int32_t* iters_dev, void* stream);
  * substeps into k chunks (clamped to the substep count). Results are the same bits for every k.
  * Env groups on their own streams fill the drain themselves and run unchunked. */
 int zb_set_step_chunks(ZbHandle* h, int k);
+
+/*
+ * Velocity commands (include/zbot_command.h: the law, the five tracking terms, the ordering).
+ * Added in ABI version 4. A handle has none until zb_set_command_config: its observations carry a
+ * zero command and no reward term reads one, exactly as before version 4.
+ *
+ * zb_set_command_config copies *cfg into the handle (waits for the device first). It takes effect
+ * at the next zb_reset or zb_step and does not resample by itself: a zb_reset draws every env's
+ * initial command; a zb_step without one continues from the commands in the state rows (zero after
+ * zb_create). NULL switches commands off. ZB_EARG with a zb_last_error text for a wrong
+ * struct_bytes, a range with lo > hi, switch_prob outside [0, 1], a non-finite field, an error
+ * scale that is not positive.
+ *
+ * With a config the step kernel adds Σ term_scale_i (level if by curriculum) term_i to the reward
+ * (and to the episode return and the statistics), writes the five unscaled terms of the last step
+ * to a buffer of the handle (zb_get_command_terms; zb_rollout: of its last step), and obs_extra
+ * carries body 1's xquat as the terms read it (ZB_X_CMD_XQUAT).
+ *
+ * zb_set_commands overwrites the commands [n_envs, 7] of the envs env_mask_dev selects (NULL: all)
+ * in the state rows: the joystick override for evaluation. The next zb_step rewards against them
+ * and its observation carries their successor; with switch_prob 0 and wz 0 that is the same
+ * command. zb_get_commands reads them back. Both work with commands off (the words are then
+ * ignored by the kernels).
+ */
+size_t zb_command_config_struct_bytes(void);
+/* the parameters of train.py's reward classes; ranges, switch_prob and scales 0 (no reference values) */
+void zb_default_command_config(ZbCommandConfig* cfg);
+/* the check zb_set_command_config runs (host only) */
+int zb_command_config_check(const ZbCommandConfig* cfg);
+int zb_set_command_config(ZbHandle* h, const ZbCommandConfig* cfg);
+int zb_set_commands(ZbHandle* h, const float* cmd_dev, const uint8_t* env_mask_dev, void* stream);
+int zb_get_commands(ZbHandle* h, float* cmd_dev, void* stream);
+int zb_get_command_terms(ZbHandle* h, float* terms_dev, void* stream);
+/* Host twins of the kernel's command path, callable without a device. env: global env ids;
+ * counter: the episode counter (initial) or rng_step (next); quat: the base quaternion qpos[3:7]
+ * (initial, next) or body 1's xquat (rewards), [n, 4]. The sampled components and the switch
+ * decisions are the device's bits; heading and the terms agree to rounding. */
+int zb_command_initial_host(const ZbCommandConfig* cfg, uint64_t seed, const uint32_t* env, const uint32_t* counter,
+                            const float* quat, float ctrl_dt, int n, float* out);
+int zb_command_next_host(const ZbCommandConfig* cfg, uint64_t seed, const uint32_t* env, const uint32_t* counter,
+                         const float* prev, const float* quat, float ctrl_dt, int n, float* out, uint8_t* switched);
+int zb_command_rewards_host(const ZbCommandConfig* cfg, const float* cmd, const float* quat, const float* vel,
+                            const float* height, int n, float* out);
 
 /* Diagnostic: one forward pass (no integration) on the qpos/qvel stored in
  * state_dev [n_envs, ZB_STATE_STRIDE] with ctrl_dev [n_envs, 20] (nullable ->

@@ -31,7 +31,7 @@ extern "C" {
 #define ZB_OBS_CRITIC    484  /* NUM_CRITIC_INPUTS, train.py:54 */
 #define ZB_OBS_EXTRA     96   /* the remaining train.py:1478-1537 observations */
 #define ZB_NUM_TERMS     12   /* reward terms registered in train.py:1546-1586 */
-#define ZB_NUM_CMD       7    /* ConstantZeroCommand, train.py:423-427 */
+#define ZB_NUM_CMD       7    /* [vx, vy, wz, heading, bh, rx, ry], train.py:205-241 (zbot_command.h; all zero without a command config) */
 #define ZB_NUM_STATS     4    /* per-env episode statistics (see ZB_ST_*) */
 
 /* ---------------- per-env state, fp32 words (u32 slots bit-cast) ------------- */
@@ -56,7 +56,7 @@ extern "C" {
 #define ZB_S_NAN         173  /* u32   flags (diagnostic): bit 0 non-finite state (sticky); bit 1 more colliders beyond the soles within reach of the floor in a substep than its banks hold (zb_bank_cap: four, or two for a model with at most two such colliders), their contacts not simulated (zb_engine.hip select_bank2; sticky); bit 2 the same in the last control step (cleared at the start of each) */
 #define ZB_S_AIR0_CONT   174  /* u32   first step of a marked rollout: contact bits (1 left, 2 right) */
 #define ZB_S_AIR0_TERM   175  /*       ... and its causal FeetAirtime term (zb_feet_airtime_exact) */
-#define ZB_S_END         176
+#define ZB_S_END         176  /* words 176..182: the velocity command (zbot_command.h ZB_S_CMD) */
 
 /* -------------- per-env randomized model parameters (config 5) -------------- */
 /* ksim randomizers named in train.py:1441-1454; sampled on every episode reset  */

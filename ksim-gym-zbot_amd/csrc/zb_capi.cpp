@@ -23,7 +23,7 @@ using zb::check_cfg;
 using zb::check_model;
 using zb::fail;
 
-#define ZB_ABI_VERSION 3
+#define ZB_ABI_VERSION 4
 
 struct ZbHandle {
   int device;
@@ -48,6 +48,9 @@ struct ZbHandle {
   int nchunk;      /* work units per pair of envs in zb_step (1: unchunked) */
   int air_mark;    /* zb_mark_rollout_start: the next zb_step / zb_rollout is a rollout's step 0 */
   int air_marked;  /* a marked step has been launched since the last zb_feet_airtime_exact */
+  int cmd_on;              /* zb_set_command_config: launches pass dccfg and run the command instantiations */
+  ZbCommandConfig* dccfg;  /* device copy of the command config */
+  float* cmd_terms;        /* [n, ZB_NUM_CMD_TERMS] unscaled tracking terms of the last step */
 };
 
 /* Chunks per control step for zb_step. The launch runs its pairs of envs in
@@ -142,6 +145,10 @@ int zb_create(const ZbModel* model, const ZbEnvConfig* cfg, int n_envs, int env_
   if (e == hipSuccess) e = hipMemset(h->sched, 0, (3 + (n + 1) / 2) * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&h->itpart, n * sizeof(int32_t));
   if (e == hipSuccess) e = hipMemset(h->itpart, 0, n * sizeof(int32_t));
+  if (e == hipSuccess) e = hipMalloc(&h->dccfg, sizeof(ZbCommandConfig));
+  if (e == hipSuccess) e = hipMemset(h->dccfg, 0, sizeof(ZbCommandConfig));
+  if (e == hipSuccess) e = hipMalloc(&h->cmd_terms, n * ZB_NUM_CMD_TERMS * sizeof(float));
+  if (e == hipSuccess) e = hipMemset(h->cmd_terms, 0, n * ZB_NUM_CMD_TERMS * sizeof(float));
   h->xg = zb::needs_xg(model);
   /* XG 4: two banks in global scratch per env (the floor selection, the sole pair) */
   /* one block per contact-row bank beyond the first (zb_engine.hip XJ_STRIDE) */
@@ -179,6 +186,8 @@ int zb_destroy(ZbHandle* h) {
   if (h->sched) (void)hipFree(h->sched);
   if (h->itpart) (void)hipFree(h->itpart);
   if (h->xj) (void)hipFree(h->xj);
+  if (h->dccfg) (void)hipFree(h->dccfg);
+  if (h->cmd_terms) (void)hipFree(h->cmd_terms);
   delete h;
   return ZB_OK;
 }
@@ -207,6 +216,8 @@ static zb::StepArgs base_args(ZbHandle* h) {
   a.ed = (h->cfg.flags & ZB_F_EULERDAMP) ? 1 : 0;
   a.sol_default = zb::solver_fields_default(h->cfg) ? 1 : 0;
   a.xj = h->xj;
+  a.cmd = h->cmd_on ? h->dccfg : nullptr;
+  a.cmd_terms = h->cmd_terms;
   return a;
 }
 
@@ -341,6 +352,44 @@ int zb_set_step_chunks(ZbHandle* h, int k) {
     h->nchunk = k > h->cfg.n_substeps ? h->cfg.n_substeps : k;
   }
   return ZB_OK;
+}
+
+int zb_set_command_config(ZbHandle* h, const ZbCommandConfig* cfg) {
+  if (!h) return fail(ZB_EARG, "zb_set_command_config: null handle");
+  if (cfg) {
+    int rc = zb::check_command_config(cfg);
+    if (rc) return rc;
+  }
+  int rc = use_device(h);
+  if (rc) return rc;
+  /* launches in flight read the device copy */
+  HIPCHK(hipDeviceSynchronize());
+  if (cfg) HIPCHK(hipMemcpy(h->dccfg, cfg, sizeof(ZbCommandConfig), hipMemcpyHostToDevice));
+  h->cmd_on = cfg ? 1 : 0;
+  return ZB_OK;
+}
+
+int zb_set_commands(ZbHandle* h, const float* cmd_dev, const uint8_t* env_mask_dev, void* stream) {
+  if (!h || (!cmd_dev && h->n > 0)) return fail(ZB_EARG, "zb_set_commands: null handle or commands");
+  int rc = use_device(h);
+  if (rc) return rc;
+  hipError_t e = zb::launch_command_copy(h->state, cmd_dev, nullptr, env_mask_dev, h->n, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_set_commands launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+int zb_get_commands(ZbHandle* h, float* cmd_dev, void* stream) {
+  if (!h || (!cmd_dev && h->n > 0)) return fail(ZB_EARG, "zb_get_commands: null handle or output");
+  int rc = use_device(h);
+  if (rc) return rc;
+  hipError_t e = zb::launch_command_copy(h->state, nullptr, cmd_dev, nullptr, h->n, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_get_commands launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+int zb_get_command_terms(ZbHandle* h, float* terms_dev, void* stream) {
+  if (!h) return fail(ZB_EARG, "null handle");
+  return copy_rows(h, terms_dev, h->cmd_terms, (size_t)h->n * ZB_NUM_CMD_TERMS * sizeof(float), stream);
 }
 
 int zb_check(ZbHandle* h) {

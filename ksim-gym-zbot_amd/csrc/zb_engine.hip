@@ -748,6 +748,7 @@ __device__ __forceinline__ void threefry2x32(uint32_t k0, uint32_t k1, uint32_t 
 #define P_PUSH 2u
 #define P_RESET 3u
 #define P_RAND 4u
+#define P_CMD ZB_RNG_CMD /* velocity commands (include/zbot_command.h) */
 __device__ __forceinline__ void rng_bits(uint64_t seed, uint32_t purpose, uint32_t k, uint32_t env, uint32_t ctr,
                                          uint32_t& a, uint32_t& b) {
   /* the key is re-derived at every draw site (opaque seed) so its round-key
@@ -4395,14 +4396,31 @@ __device__ __forceinline__ void rotate_quat_by_quat(const float q_[4], const flo
 }
 
 /* observation assembly + obs-derived carries (train.py:1478-1537, 1624-1679) */
+/* CM: velocity commands (include/zbot_command.h). cv: lane k < 7 holds word k of the command this
+   observation carries */
+template <bool CM = false>
 __device__ __forceinline__ void observe(const Ctx& c, EnvS& s, const LaneS& ls, const BodyK& B, const Sensors& sen, float* oa,
-                        float* oc, float* ox) {
+                        float* oc, float* ox, float cv = 0.f) {
   MP m = c.m;
   CP cfg = c.cfg;
   const int l = c.l;
   /* ImuOrientationObservation (heading command 0) */
   float hq[4] = {1.f, 0.f, 0.f, 0.f}, bq[4];
   rotate_quat_by_quat(sen.fq, hq, true, bq);
+  float ca = 0.f; /* the actor's command slot of lanes 4..9: words 0, 1, 3, 4, 5, 6 */
+  if constexpr (CM) {
+    /* spun back by the heading command (train.py:860-867). A heading of exactly 0 keeps the form
+       above, whose constant quaternion the compiler folds: a zero command then gives the bits of
+       a handle without commands */
+    const float h = tsh(cv, ZB_C_HEADING);
+    float sh, ch;
+    sincosf(0.5f * h, &sh, &ch);
+    float hv[4] = {ch, 0.f, 0.f, sh}, bh[4];
+    rotate_quat_by_quat(sen.fq, hv, true, bh);
+    for (int k = 0; k < 4; k++) bq[k] = h == 0.f ? bq[k] : bh[k];
+    const int j = l - 4, src = j < 2 ? j : j + 1;
+    ca = tsh(cv, (src < 0 || src >= ZB_CMD_WORDS) ? 0 : src);
+  }
   if (bq[0] < 0.f) for (int k = 0; k < 4; k++) bq[k] = -bq[k];
   float imu[4];
   for (int k = 0; k < 4; k++) {
@@ -4454,7 +4472,7 @@ __device__ __forceinline__ void observe(const Ctx& c, EnvS& s, const LaneS& ls, 
       oa[ZB_NJ + l] = va;
     }
     if (l < 4) oa[40 + l] = imu[l];
-    if (l >= 4 && l < 10) oa[40 + l] = 0.f;
+    if (l >= 4 && l < 10) oa[40 + l] = CM ? ca : 0.f;
   }
   if (oc) {
     if (l < ZB_NJ) {
@@ -4469,7 +4487,7 @@ __device__ __forceinline__ void observe(const Ctx& c, EnvS& s, const LaneS& ls, 
     if (l < 3) oc[440 + l] = acc[l];
     if (l < 3) oc[443 + l] = sen.gyro[l];
     if (l < 4) oc[446 + l] = imu[l];
-    if (l < ZB_NUM_CMD) oc[450 + l] = 0.f;
+    if (l < ZB_NUM_CMD) oc[450 + l] = CM ? cv : 0.f;
     if (l < 3) oc[477 + l] = s.bp[l];
     if (l < 4) oc[480 + l] = s.bq[l];
   }
@@ -4495,6 +4513,16 @@ __device__ __forceinline__ void observe(const Ctx& c, EnvS& s, const LaneS& ls, 
       ox[ZB_X_ACT_ACC + l] = acca;
     }
     for (int i = ZB_X_END + l; i < ZB_OBS_EXTRA; i += TEAM) ox[i] = 0.f;
+    if constexpr (CM) {
+      /* body 1's orientation as the command terms read it (the lane that zeroed the slot) */
+      float xq = 0.f;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float v = tsh(B.xq[k], 1);
+        xq = k == l ? v : xq;
+      }
+      if (l < 4) ox[ZB_X_CMD_XQUAT + l] = xq;
+    }
   }
 }
 
@@ -4598,6 +4626,55 @@ __device__ __forceinline__ bool rewards(const Ctx& c, EnvS& s, const LaneS& ls, 
   s.ep_steps = steps;
   s.ep_ret += total;
   return done;
+}
+
+/* ---------------------------- velocity commands ----------------------------- */
+/* include/zbot_command.h has the law, the terms and the ordering. The env's command sits in one
+   register across the launch: lane k < 7 holds word k (cv). Every lane of the team evaluates the
+   law on the same inputs, once per control step. */
+__device__ __forceinline__ void cmd_uniforms(const Ctx& c, uint32_t k0, uint32_t ctr, float u[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) uniform2(cseed(c), P_CMD, k0 + (uint32_t)k, cenv(c), ctr, u[2 * k], u[2 * k + 1]);
+}
+__device__ __forceinline__ void cmd_words(float cv, float cmd[ZB_CMD_WORDS]) {
+#pragma unroll
+  for (int k = 0; k < ZB_CMD_WORDS; k++) cmd[k] = tsh(cv, k);
+}
+template <int N>
+__device__ __forceinline__ float lane_word(const Ctx& c, const float w[N]) {
+  float v = 0.f;
+#pragma unroll
+  for (int k = 0; k < N; k++) v = k == c.l ? w[k] : v;
+  return v;
+}
+/* the initial command of episode `episode` at the pose in s.bq (reset_prepare ran) */
+__device__ __forceinline__ float cmd_initial(const Ctx& c, const EnvS& s, const ZbCommandConfig* cc, uint32_t episode) {
+  float u[8], cmd[ZB_CMD_WORDS];
+  cmd_uniforms(c, ZB_CMD_K_RESET, episode, u);
+  const float bq[4] = {s.bq[0], s.bq[1], s.bq[2], s.bq[3]};
+  zbc_initial(cc, u, zbc_yaw(bq), c.cfg->ctrl_dt, cmd);
+  return lane_word<ZB_CMD_WORDS>(c, cmd);
+}
+/* End of a control step, after rewards(): the five terms on cmd_t (returned unscaled in ct, their
+   weighted sum in the return value), then cv becomes cmd_{t+1} at the post-step base quaternion */
+__device__ __forceinline__ float cmd_step(const Ctx& c, const EnvS& s, const LaneS& ls, const BodyK& B,
+                                          const ZbCommandConfig* cc, float cur, float& cv, float ct[ZB_NUM_CMD_TERMS]) {
+  float cmd[ZB_CMD_WORDS], xq1[4], vel[3];
+  cmd_words(cv, cmd);
+#pragma unroll
+  for (int k = 0; k < 4; k++) xq1[k] = tsh(B.xq[k], 1);
+#pragma unroll
+  for (int k = 0; k < 3; k++) vel[k] = tsh(ls.v, k);
+  const float hz = tsh(B.xp[2], 1);
+  zbc_rewards(cc, cmd, xq1, vel, hz, ct);
+  const float total = zbc_reward_sum(cc, ct, cur);
+  float u[8], us, u_unused, cn[ZB_CMD_WORDS];
+  uniform2(cseed(c), P_CMD, ZB_CMD_K_SWITCH, cenv(c), s.rng_step, us, u_unused);
+  cmd_uniforms(c, ZB_CMD_K_REDRAW, s.rng_step, u);
+  const float bq[4] = {s.bq[0], s.bq[1], s.bq[2], s.bq[3]};
+  zbc_next(cc, cmd, us, u, zbc_yaw(bq), c.cfg->ctrl_dt, cn);
+  cv = lane_word<ZB_CMD_WORDS>(c, cn);
+  return total;
 }
 
 /* ------------------------------ state I/O ---------------------------------- */
@@ -4839,8 +4916,11 @@ constexpr bool SMOOTH_DIET = SOLVER == ZB_SOLVER_CG
    compiles to the parent's instructions */
 template <int SOLVER, int XG, int ED, bool DS>
 constexpr bool CONST_REC = DS;
-/* DS: the copy for handles whose solver fields are the defaults (sol_iterations; SOL_LITERAL) */
-template <int SOLVER, int XG, int ED, bool DS = false>
+/* DS: the copy for handles whose solver fields are the defaults (sol_iterations; SOL_LITERAL).
+   CM: the copy for handles with a command config (a.cmd; include/zbot_command.h): the command path
+   runs once per control step, never inside the substep loop, and every `if constexpr (CM)` below is
+   absent from the CM = false instantiations, which compile to the instructions they had before */
+template <int SOLVER, int XG, int ED, bool DS = false, bool CM = false>
 __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   const int team = threadIdx.x / TEAM;
   /* Chunked step (a.nchunk > 1, one control step): the launch has npair * nchunk workgroups, each
@@ -4918,6 +4998,10 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   if (K > 1) load_state<true>(c, s, ls, state_row());
   else load_state<false>(c, s, ls, state_row());
   load_params<SD>(c, s, ls, rand_row());
+  float cv = 0.f; /* CM: lane k < 7 holds word k of the env's command */
+  if constexpr (CM) {
+    if (c.l < ZB_CMD_WORDS) cv = K > 1 ? ld_cg<true>(state_row() + ZB_S_CMD + c.l) : ld_cg<false>(state_row() + ZB_S_CMD + c.l);
+  }
 #ifdef ZB_BLOCKCOUNT
   COUNT(BC_PROLOGUE_CYC, zb_now() - bc_t0); /* make_ctx, load_state, load_params */
 #endif
@@ -4996,6 +5080,16 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
         float air_term;
         done = rewards(c, s, ls, B, a.curriculum, terms, total, fail, air_term);
         success = done && !fail;
+        if constexpr (CM) {
+          /* the tracking terms on cmd_t, then cmd_{t+1} (a reset below replaces it) */
+          float ct[ZB_NUM_CMD_TERMS];
+          const float ctot = cmd_step(c, s, ls, B, a.cmd, a.curriculum, cv, ct);
+          total += ctot;
+          s.ep_ret += ctot;
+          const float ctl = lane_word<ZB_NUM_CMD_TERMS>(c, ct);
+          if (live && last_t && a.cmd_terms && c.l < ZB_NUM_CMD_TERMS)
+            a.cmd_terms[(size_t)vopq(e) * ZB_NUM_CMD_TERMS + c.l] = ctl;
+        }
         if (a.air_mark && t == 0 && live && c.l == 0) {
           /* first step of a rollout: its contact flags and causal FeetAirtime term, for the
              exact ksim form patched in after the rollout (airtime_exact_kernel) */
@@ -5022,14 +5116,15 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
       if (!ghost && (resetting || !done_reset)) {
         const bool out = live && last_t;
         const size_t eo = (size_t)vopq(e);
-        observe(c, s, ls, B, sen, (out && a.obs_actor) ? a.obs_actor + eo * ZB_OBS_ACTOR : nullptr,
-                (out && a.obs_critic) ? a.obs_critic + eo * ZB_OBS_CRITIC : nullptr,
-                (out && a.obs_extra) ? a.obs_extra + eo * ZB_OBS_EXTRA : nullptr);
+        observe<CM>(c, s, ls, B, sen, (out && a.obs_actor) ? a.obs_actor + eo * ZB_OBS_ACTOR : nullptr,
+                    (out && a.obs_critic) ? a.obs_critic + eo * ZB_OBS_CRITIC : nullptr,
+                    (out && a.obs_extra) ? a.obs_extra + eo * ZB_OBS_EXTRA : nullptr, cv);
       }
       if (resetting || ghost) break;
       if (__ballot(done_reset) == 0ull) break;
       if (done_reset) {
         reset_prepare<SD>(c, s, ls, rand_row());
+        if constexpr (CM) cv = cmd_initial(c, s, a.cmd, s.episode - 1u); /* the new episode's, at the reset pose */
         resetting = true;
       } else {
         ghost = true;
@@ -5056,6 +5151,12 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
   if (live && !timed_out) {
     if (K > 1) store_state<true>(c, s, ls, state_row());
     else store_state<false>(c, s, ls, state_row());
+    if constexpr (CM) {
+      if (c.l < ZB_CMD_WORDS) {
+        if (K > 1) st_cg<true>(state_row() + ZB_S_CMD + c.l, cv);
+        else st_cg<false>(state_row() + ZB_S_CMD + c.l, cv);
+      }
+    }
   }
   if (K > 1) {
     /* publish: every state store of this wave happens-before lane 0's flag store */
@@ -5121,12 +5222,20 @@ __global__ __launch_bounds__(64) void reset_kernel(StepArgs a) {
   int it = 0;
   if (live) reset_prepare(c, s, ls, rnd);
   else load_params(c, s, ls, nullptr);
+  /* commands on (a kernel argument, so the branch is wave-uniform): the initial command of the new
+     episode at the reset pose */
+  const bool cm = a.cmd != nullptr;
+  float cv = 0.f;
+  if (cm && live) cv = cmd_initial(c, s, a.cmd, s.episode - 1u);
   forward<SOLVER, XG>(c, s, ls, B, r, live, sen, it);
   if (!live) return;
-  observe(c, s, ls, B, sen, a.obs_actor ? a.obs_actor + (size_t)e * ZB_OBS_ACTOR : nullptr,
-          a.obs_critic ? a.obs_critic + (size_t)e * ZB_OBS_CRITIC : nullptr,
-          a.obs_extra ? a.obs_extra + (size_t)e * ZB_OBS_EXTRA : nullptr);
+  float* const oa = a.obs_actor ? a.obs_actor + (size_t)e * ZB_OBS_ACTOR : nullptr;
+  float* const oc = a.obs_critic ? a.obs_critic + (size_t)e * ZB_OBS_CRITIC : nullptr;
+  float* const ox = a.obs_extra ? a.obs_extra + (size_t)e * ZB_OBS_EXTRA : nullptr;
+  if (cm) observe<true>(c, s, ls, B, sen, oa, oc, ox, cv);
+  else observe(c, s, ls, B, sen, oa, oc, ox);
   store_state(c, s, ls, st);
+  if (cm && c.l < ZB_CMD_WORDS) st[ZB_S_CMD + c.l] = cv;
 }
 
 /* single forward on the stored (qpos, qvel), ctrl = action row; dumps internals */
@@ -5271,12 +5380,13 @@ hipError_t ZB_EP(launch_step)(const StepArgs& a, hipStream_t s) {
   with_variant(b.solver, b.xg, b.ed, [&](auto S, auto X, auto D) {
     constexpr int SV = decltype(S)::value, XV = decltype(X)::value, DV = decltype(D)::value;
     if constexpr (SOL_LITERAL<SV, XV, DV>) {
-      if (b.sol_default) {
+      if (b.sol_default && !b.cmd) {
         hipLaunchKernelGGL((step_kernel<SV, XV, DV, true>), grid, block, 0, s, b);
         return;
       }
     }
-    hipLaunchKernelGGL((step_kernel<SV, XV, DV>), grid, block, 0, s, b);
+    if (b.cmd) hipLaunchKernelGGL((step_kernel<SV, XV, DV, false, true>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((step_kernel<SV, XV, DV>), grid, block, 0, s, b);
   });
   return hipGetLastError();
 }
@@ -5316,6 +5426,29 @@ hipError_t launch_airtime_exact(const StepArgs& a, hipStream_t s) {
   dim3 grid((unsigned)((a.n_envs + 255) / 256)), block(256);
   hipLaunchKernelGGL(airtime_exact_kernel, grid, block, 0, s, (const float*)a.state, a.cfg, a.n_envs, a.curriculum,
                      a.reward, a.reward_terms, a.stats);
+  return hipGetLastError();
+}
+#endif
+
+#ifndef ZB_ENGINE_TU_B
+/* zb_set_commands / zb_get_commands: one thread per command word, between a packed [n, 7] array and
+   the state rows (in == null: state -> out; else in -> state for the envs the mask selects) */
+__global__ __launch_bounds__(256) void command_copy_kernel(float* state, const float* in, float* out, const uint8_t* mask,
+                                                           int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * ZB_CMD_WORDS) return;
+  const int e = i / ZB_CMD_WORDS, k = i - e * ZB_CMD_WORDS;
+  float* w = state + (size_t)e * ZB_STATE_STRIDE + ZB_S_CMD + k;
+  if (in) {
+    if (!mask || mask[e]) *w = in[i];
+  } else {
+    out[i] = *w;
+  }
+}
+hipError_t launch_command_copy(float* state, const float* in, float* out, const uint8_t* mask, int n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  dim3 grid((unsigned)((n * ZB_CMD_WORDS + 255) / 256)), block(256);
+  hipLaunchKernelGGL(command_copy_kernel, grid, block, 0, s, state, in, out, mask, n);
   return hipGetLastError();
 }
 #endif

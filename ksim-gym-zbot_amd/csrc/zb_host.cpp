@@ -4,7 +4,9 @@
  * and the learner's host twins (include/zbot_ppo.h "Learner": zb_ppo_loss_host,
  * zb_grad_sqnorm_host, zb_adamw_step_host), the CPU bit reference of csrc/zb_learner.hip; and
  * the minibatch twins ("Minibatches": zb_minibatch_perm_host, zb_minibatch_gather_host), that of
- * csrc/zb_minibatch.hip.
+ * csrc/zb_minibatch.hip; and the velocity commands' twins (include/zbot_command.h:
+ * zb_command_initial_host, zb_command_next_host, zb_command_rewards_host), built on the header the
+ * step kernel includes.
  * Plain C++ (no HIP): the product library links it, and csrc/sanitize.mk builds it with the host
  * sanitizers for tests/test_sanitizers.py.
  */
@@ -19,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "zbot_command.h"
 #include "zbot_fmath.h"
 #include "zbot_learner_math.h"
 #include "zbot_ppo.h"
@@ -243,6 +246,37 @@ int check_cfg(const ZbEnvConfig* c) {
 /* The per-lane roles of a 32-lane team (body lane, dof lane, limb-chain position, contact
    rows holding the dof, actuator), computed once here instead of by every wave at the top
    of every launch. Field-major [TP_NF][32]; the checks of check_model hold. */
+int check_command_config(const ZbCommandConfig* c) {
+  if (!c) return fail(ZB_EARG, "command config: null");
+  if (c->struct_bytes != (int32_t)sizeof(ZbCommandConfig))
+    return fail(ZB_EARG, "command config: struct_bytes %d != %zu", c->struct_bytes, sizeof(ZbCommandConfig));
+  /* every fp32 field is finite (the flags between term_scale and the parameters are integers) */
+  const float* f = &c->vx_range[0];
+  const float* const flags = reinterpret_cast<const float*>(&c->term_by_curriculum[0]);
+  const float* const end = reinterpret_cast<const float*>(c + 1);
+  for (; f < end; f++) {
+    if (f >= flags && f < flags + ZB_NUM_CMD_TERMS) continue;
+    if (!std::isfinite(*f))
+      return fail(ZB_EARG, "command config: non-finite field at byte %d", (int)((const char*)f - (const char*)c));
+  }
+  const struct { const char* name; const float* r; } ranges[] = {
+      {"vx_range", c->vx_range}, {"vy_range", c->vy_range}, {"wz_range", c->wz_range}, {"bh_range", c->bh_range},
+      {"bh_standing_range", c->bh_standing_range}, {"rx_range", c->rx_range}, {"ry_range", c->ry_range}};
+  for (const auto& r : ranges)
+    if (r.r[0] > r.r[1] || !std::isfinite(r.r[1] - r.r[0]))
+      return fail(ZB_EARG, "command config: %s lo %g > hi %g (or a width beyond fp32)", r.name, r.r[0], r.r[1]);
+  if (!(c->switch_prob >= 0.f && c->switch_prob <= 1.f))
+    return fail(ZB_EARG, "command config: switch_prob %g outside [0, 1]", c->switch_prob);
+  if (c->dead_zone < 0.f) return fail(ZB_EARG, "command config: dead_zone %g < 0", c->dead_zone);
+  const struct { const char* name; float v; } pos[] = {{"linvel_error_scale", c->linvel_error_scale},
+                                                       {"yaw_error_scale", c->yaw_error_scale},
+                                                       {"xy_orient_error_scale", c->xy_orient_error_scale},
+                                                       {"base_height_error_scale", c->base_height_error_scale}};
+  for (const auto& q : pos)
+    if (!(q.v > 0.f)) return fail(ZB_EARG, "command config: %s %g must be > 0", q.name, q.v);
+  return ZB_OK;
+}
+
 void build_topology(const ZbModel* m, int32_t t[zb::TP_NF][zb::TOPO_LANES]) {
   const int NB = ZB_NBODY_TASK, NV = 6 + ZB_NJ;
   memset(t, 0, sizeof(int32_t) * TP_NF * TOPO_LANES);
@@ -552,6 +586,76 @@ int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int 
       }
   }
   return ZB_OK;
+}
+
+/* ---- velocity commands: the host twins of the step kernel's command path ---- */
+static void command_uniforms(uint64_t seed, uint32_t k0, uint32_t env, uint32_t ctr, float u[8]) {
+  for (uint32_t k = 0; k < 4; k++) {
+    uint32_t a, b;
+    zbf_rng_bits(seed, ZB_RNG_CMD, k0 + k, env, ctr, &a, &b);
+    u[2 * k] = zbf_u01(a);
+    u[2 * k + 1] = zbf_u01(b);
+  }
+}
+
+size_t zb_command_config_struct_bytes(void) { return sizeof(ZbCommandConfig); }
+
+int zb_command_config_check(const ZbCommandConfig* cfg) { return zb::check_command_config(cfg); }
+
+int zb_command_initial_host(const ZbCommandConfig* cfg, uint64_t seed, const uint32_t* env, const uint32_t* counter,
+                            const float* quat, float ctrl_dt, int n, float* out) {
+  if (int rc = zb::check_command_config(cfg)) return rc;
+  if (n < 0 || (n > 0 && (!env || !counter || !quat || !out)))
+    return fail(ZB_EARG, "zb_command_initial_host: null pointer or n = %d", n);
+  for (int i = 0; i < n; i++) {
+    float u[8];
+    command_uniforms(seed, ZB_CMD_K_RESET, env[i], counter[i], u);
+    zbc_initial(cfg, u, zbc_yaw(quat + 4 * (size_t)i), ctrl_dt, out + 7 * (size_t)i);
+  }
+  return ZB_OK;
+}
+
+int zb_command_next_host(const ZbCommandConfig* cfg, uint64_t seed, const uint32_t* env, const uint32_t* counter,
+                         const float* prev, const float* quat, float ctrl_dt, int n, float* out, uint8_t* switched) {
+  if (int rc = zb::check_command_config(cfg)) return rc;
+  if (n < 0 || (n > 0 && (!env || !counter || !prev || !quat || !out)))
+    return fail(ZB_EARG, "zb_command_next_host: null pointer or n = %d", n);
+  for (int i = 0; i < n; i++) {
+    float u[8], cmd[7];
+    uint32_t a, b;
+    zbf_rng_bits(seed, ZB_RNG_CMD, ZB_CMD_K_SWITCH, env[i], counter[i], &a, &b);
+    command_uniforms(seed, ZB_CMD_K_REDRAW, env[i], counter[i], u);
+    const int sw = zbc_next(cfg, prev + 7 * (size_t)i, zbf_u01(a), u, zbc_yaw(quat + 4 * (size_t)i), ctrl_dt, cmd);
+    memcpy(out + 7 * (size_t)i, cmd, sizeof cmd); /* out may be prev */
+    if (switched) switched[i] = (uint8_t)sw;
+  }
+  return ZB_OK;
+}
+
+int zb_command_rewards_host(const ZbCommandConfig* cfg, const float* cmd, const float* quat, const float* vel,
+                            const float* height, int n, float* out) {
+  if (int rc = zb::check_command_config(cfg)) return rc;
+  if (n < 0 || (n > 0 && (!cmd || !quat || !vel || !height || !out)))
+    return fail(ZB_EARG, "zb_command_rewards_host: null pointer or n = %d", n);
+  for (int i = 0; i < n; i++)
+    zbc_rewards(cfg, cmd + 7 * (size_t)i, quat + 4 * (size_t)i, vel + 3 * (size_t)i, height[i],
+                out + ZB_NUM_CMD_TERMS * (size_t)i);
+  return ZB_OK;
+}
+
+void zb_default_command_config(ZbCommandConfig* c) {
+  if (!c) return;
+  memset(c, 0, sizeof *c);
+  c->struct_bytes = (int32_t)sizeof(ZbCommandConfig);
+  c->dead_zone = 0.09f;
+  c->linvel_error_scale = 0.25f;
+  c->yaw_error_scale = 0.25f;
+  c->xy_orient_error_scale = 0.25f;
+  c->base_height_error_scale = 0.25f;
+  c->stand_still_threshold = 1e-2f;
+  c->l1_slope = 1.0f;
+  c->l1_target_bonus = 2.0f;
+  c->standard_height = 0.27f;
 }
 
 const char* zb_last_error(void) { return zb::g_err.c_str(); }

@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "zbot.h"
+#include "zbot_command.h"
 #include "zbot_ppo.h"
 
 namespace zb {
@@ -62,6 +63,8 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 /* ZB_OK, or ZB_EARG / ZB_EMODEL with the reason in zb_last_error() */
 int check_model(const ZbModel* m);
 int check_cfg(const ZbEnvConfig* c);
+/* zb_set_command_config's check: struct_bytes, finite fields, lo <= hi, switch_prob in [0, 1] */
+int check_command_config(const ZbCommandConfig* c);
 /* the model needs the general-collider kernels (anything but exactly two box soles) */
 int needs_xg(const ZbModel* m); /* 0 two-sole, 1 general colliders, 2 with cylinders / ellipsoids / meshes, 3 the sole pair alone, 4 the sole pair beside up to two other colliders, 5 more than two colliders beyond the soles (two floor banks), 6 the sole pair beside more than two (two floor banks and the pair's) */
 /* floor colliders beyond the soles that a substep holds before the overflow flag is set (zb_bank_cap) */

@@ -10,7 +10,11 @@
  * replaced by small integers, boundary values or random bits (deterministic xorshift). Every
  * copy that passes validation is handed to build_topology, which must then stay inside the
  * model's arrays: an out-of-bounds index the validation let through is an ASan / UBSan report
- * (-fsanitize=bounds sees the fixed-size member arrays). Prints one summary line.
+ * (-fsanitize=bounds sees the fixed-size member arrays). The velocity commands' host twins
+ * (include/zbot_command.h) get the same treatment: a joystick ZbCommandConfig with one word
+ * corrupted goes to zb_command_config_check, and every copy that passes runs
+ * zb_command_initial_host / _next_host / _rewards_host over a small batch whose outputs must then
+ * lie where the law puts them. Prints one summary line.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -98,8 +102,67 @@ int main(int argc, char** argv) {
     cw[next_u64() % (sizeof c / 4)] = (uint32_t)next_u64();
     (void)zb::check_cfg(&c);
   }
-  printf("zb_host_selftest ok: %ld mutations, %ld accepted, %ld rejected, words %zu\n", mutations, accepted,
-         rejected, words);
+  /* the command twins */
+  ZbCommandConfig cc;
+  zb_default_command_config(&cc);
+  const float ranges[7][2] = {{-0.3f, 0.8f}, {-0.4f, 0.4f}, {-1.f, 1.f}, {-0.05f, 0.02f}, {-0.08f, 0.f}, {-0.2f, 0.2f},
+                              {-0.25f, 0.15f}};
+  memcpy(cc.vx_range, ranges, sizeof ranges);
+  cc.switch_prob = 0.25f;
+  if (zb_command_config_check(&cc) != ZB_OK) {
+    fprintf(stderr, "the joystick command config fails validation: %s\n", zb_last_error());
+    return 1;
+  }
+  const int nb = 64;
+  std::vector<uint32_t> env(nb), ctr(nb);
+  std::vector<float> quat(4 * nb), cmd(7 * nb), nxt(7 * nb), vel(3 * nb), hz(nb), terms(ZB_NUM_CMD_TERMS * nb);
+  std::vector<uint8_t> sw(nb);
+  long cmd_accepted = 0, cmd_rejected = 0;
+  for (long it = 0; it < mutations / 8 + 1; it++) {
+    ZbCommandConfig c = cc;
+    if (it > 0) reinterpret_cast<uint32_t*>(&c)[next_u64() % (sizeof c / 4)] = (uint32_t)next_u64();
+    if (zb_command_config_check(&c) != ZB_OK) {
+      cmd_rejected++;
+      continue;
+    }
+    cmd_accepted++;
+    for (int i = 0; i < nb; i++) {
+      env[i] = (uint32_t)next_u64();
+      ctr[i] = (uint32_t)next_u64();
+      float n2 = 0.f;
+      for (int k = 0; k < 4; k++) {
+        quat[4 * i + k] = (float)((double)(next_u64() >> 11) / 9007199254740992.0 * 2.0 - 1.0);
+        n2 += quat[4 * i + k] * quat[4 * i + k];
+      }
+      if (n2 < 1e-3f) quat[4 * i] = 1.f;
+      for (int k = 0; k < 3; k++) vel[3 * i + k] = (float)((double)(next_u64() >> 11) / 9007199254740992.0 - 0.5);
+      hz[i] = 0.05f + 0.4f * (float)((double)(next_u64() >> 11) / 9007199254740992.0);
+    }
+    const uint64_t seed = next_u64();
+    if (zb_command_initial_host(&c, seed, env.data(), ctr.data(), quat.data(), 0.02f, nb, cmd.data()) != ZB_OK ||
+        zb_command_next_host(&c, seed, env.data(), ctr.data(), cmd.data(), quat.data(), 0.02f, nb, nxt.data(),
+                             sw.data()) != ZB_OK ||
+        zb_command_rewards_host(&c, nxt.data(), quat.data(), vel.data(), hz.data(), nb, terms.data()) != ZB_OK) {
+      fprintf(stderr, "a command twin rejected a validated config: %s\n", zb_last_error());
+      return 1;
+    }
+    for (int i = 0; i < nb; i++) {
+      const float* v = &cmd[7 * i];
+      const bool in_x = v[0] == 0.f || (v[0] >= c.vx_range[0] && v[0] <= c.vx_range[1]);
+      const bool in_y = v[1] == 0.f || (v[1] >= c.vy_range[0] && v[1] <= c.vy_range[1]);
+      const bool in_w = v[2] == 0.f || (v[2] >= c.wz_range[0] && v[2] <= c.wz_range[1]);
+      if (!in_x || !in_y || !in_w || sw[i] > 1) {
+        fprintf(stderr, "command %d outside its ranges: %g %g %g (switched %d)\n", i, v[0], v[1], v[2], sw[i]);
+        return 1;
+      }
+      if (!sw[i] && memcmp(&nxt[7 * i], v, 3 * sizeof(float)) != 0) {
+        fprintf(stderr, "command %d changed without a switch\n", i);
+        return 1;
+      }
+    }
+  }
+  printf("zb_host_selftest ok: %ld mutations, %ld accepted, %ld rejected, words %zu; command configs %ld accepted, "
+         "%ld rejected\n", mutations, accepted, rejected, words, cmd_accepted, cmd_rejected);
   delete m;
   delete model;
   return 0;

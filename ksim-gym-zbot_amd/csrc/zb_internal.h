@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "zbot.h"
+#include "zbot_command.h"
 #include "zbot_policy.h"
 #include "zbot_ppo.h"
 #include "zb_host.h"
@@ -63,6 +64,9 @@ struct StepArgs {
   int ed;                   /* ZB_F_EULERDAMP: the step kernel integrates the joint damping implicitly */
   int sol_default;          /* the handle's solver fields are the defaults (solver_fields_default): launch_step may
                                run the instantiation that holds them as literals */
+  /* velocity commands (include/zbot_command.h), appended so the fields above keep their offsets */
+  const ZbCommandConfig* cmd; /* device copy, or null: commands off (the instantiations without the command path) */
+  float* cmd_terms;           /* [n, ZB_NUM_CMD_TERMS] unscaled tracking terms of the last step */
 };
 
 /* The solver fields of zb_default_config (MuJoCo's opt.tolerance / ls_tolerance defaults, train.py's
@@ -87,6 +91,8 @@ hipError_t launch_debug_forward(const StepArgs& a, hipStream_t s);
 /* exact ksim FeetAirtime row 0 of a marked rollout (a.state, a.cfg, a.n_envs, a.curriculum,
    a.reward = reward row 0 or null, a.reward_terms = terms row 0 or null) */
 hipError_t launch_airtime_exact(const StepArgs& a, hipStream_t s);
+/* packed [n, 7] commands <-> state rows: in != null writes the envs `mask` selects (null: all), else reads into out */
+hipError_t launch_command_copy(float* state, const float* in, float* out, const uint8_t* mask, int n, hipStream_t s);
 
 /* post-rollout PPO inputs (zb_ppo.hip, include/zbot_ppo.h) */
 struct GaeArgs {

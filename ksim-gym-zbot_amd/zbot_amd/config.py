@@ -91,6 +91,53 @@ def default_config(
     return c
 
 
+def command_config(
+    *,
+    vx_range: tuple[float, float],
+    vy_range: tuple[float, float],
+    wz_range: tuple[float, float],
+    bh_range: tuple[float, float],
+    bh_standing_range: tuple[float, float],
+    rx_range: tuple[float, float],
+    ry_range: tuple[float, float],
+    switch_prob: float,
+    scales: dict | None = None,
+    by_curriculum: tuple[str, ...] = (),
+    dead_zone: float = 0.09,
+    error_scale: float = 0.25,
+    stand_still_threshold: float = 1e-2,
+    l1_slope: float = 1.0,
+    l1_target_bonus: float = 2.0,
+    standard_height: float = 0.27,
+) -> cs.ZbCommandConfig:
+    """The velocity command config (include/zbot_command.h): UnifiedCommand's seven ranges and
+    switch_prob (train.py:189-261; required, the reference never instantiates it, so they have no
+    reference values) and the five tracking terms. `scales` maps names of cs.CMD_TERM_NAMES to the
+    term's reward scale (default 0: computed and reported, not rewarded); `by_curriculum` names the
+    terms whose scale is multiplied by the curriculum level. The other parameters default to the
+    reference's class defaults (train.py:215-217, 281-285, 320-324, 472-473)."""
+    c = cs.ZbCommandConfig()
+    c.struct_bytes = ctypes.sizeof(cs.ZbCommandConfig)
+    for name, r in (("vx_range", vx_range), ("vy_range", vy_range), ("wz_range", wz_range), ("bh_range", bh_range),
+                    ("bh_standing_range", bh_standing_range), ("rx_range", rx_range), ("ry_range", ry_range)):
+        lo, hi = r
+        getattr(c, name)[0], getattr(c, name)[1] = lo, hi
+    c.switch_prob = switch_prob
+    c.dead_zone = dead_zone
+    unknown = (set(scales or {}) | set(by_curriculum)) - set(cs.CMD_TERM_NAMES)
+    if unknown:
+        raise ValueError(f"unknown command terms {sorted(unknown)}; the terms are {cs.CMD_TERM_NAMES}")
+    for i, name in enumerate(cs.CMD_TERM_NAMES):
+        c.term_scale[i] = (scales or {}).get(name, 0.0)
+        c.term_by_curriculum[i] = 1 if name in by_curriculum else 0
+    c.linvel_error_scale = c.yaw_error_scale = c.xy_orient_error_scale = c.base_height_error_scale = error_scale
+    c.stand_still_threshold = stand_still_threshold
+    c.l1_slope = l1_slope
+    c.l1_target_bonus = l1_target_bonus
+    c.standard_height = standard_height
+    return c
+
+
 def config_flags(c: cs.ZbEnvConfig) -> dict:
     return {
         "obs_noise": bool(c.flags & cs.F_OBS_NOISE),

@@ -31,7 +31,9 @@ CRITIC_DIM = dict(
 NUM_ACTOR_INPUTS = sum(ACTOR_DIM.values())  # 50, train.py:53
 NUM_CRITIC_INPUTS = sum(CRITIC_DIM.values())  # 484, train.py:54
 
-COMMAND_NAME = "zero_command"  # train.py:56
+COMMAND_NAME = "zero_command"  # train.py:56: the name the reference registers its command under. The seven words are
+# [vx, vy, wz, heading, bh, rx, ry] (train.py:205-241): all zero without a command config, UnifiedCommand's law with
+# one (include/zbot_command.h, config.command_config)
 
 # (joint_name, reference_angle_rad, weight) in network-output (= ctrl = qpos[7:]) order, train.py:61-82
 JOINT_BIASES: list[tuple[str, float, float]] = [

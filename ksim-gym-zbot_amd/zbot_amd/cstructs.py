@@ -279,5 +279,42 @@ class ZbEnvConfig(C.Structure):
     ]
 
 
+# include/zbot_command.h
+CMD_WORDS = 7
+S_CMD = 176  # state words 176..182: vx, vy, wz, heading, bh, rx, ry
+NUM_CMD_TERMS = 5
+CT_LINVEL, CT_LINVEL_L1, CT_YAW, CT_XY_ORIENT, CT_BASE_HEIGHT = range(5)
+CMD_TERM_NAMES = ("linvel_tracking", "linvel_tracking_l1", "yaw_tracking", "xy_orientation", "base_height")
+X_CMD_XQUAT = 67  # obs_extra [4], commands on: body 1's xquat as the command terms read it
+RNG_CMD = 5
+CMD_K_RESET, CMD_K_SWITCH, CMD_K_REDRAW = 0, 4, 8
+
+
+class ZbCommandConfig(C.Structure):
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("vx_range", _f(2)),
+        ("vy_range", _f(2)),
+        ("wz_range", _f(2)),
+        ("bh_range", _f(2)),
+        ("bh_standing_range", _f(2)),
+        ("rx_range", _f(2)),
+        ("ry_range", _f(2)),
+        ("switch_prob", C.c_float),
+        ("dead_zone", C.c_float),
+        ("term_scale", _f(NUM_CMD_TERMS)),
+        ("term_by_curriculum", _i(NUM_CMD_TERMS)),
+        ("linvel_error_scale", C.c_float),
+        ("yaw_error_scale", C.c_float),
+        ("xy_orient_error_scale", C.c_float),
+        ("base_height_error_scale", C.c_float),
+        ("stand_still_threshold", C.c_float),
+        ("l1_slope", C.c_float),
+        ("l1_target_bonus", C.c_float),
+        ("standard_height", C.c_float),
+        ("pad", _f(1)),
+    ]
+
+
 def struct_field_names(cls: type) -> list[str]:
     return [name for name, _ in cls._fields_]

@@ -13,7 +13,7 @@ import os
 from . import cstructs as cs
 
 LIB_NAME = "libzbot_hip.so"
-ABI_VERSION = 3  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch
+ABI_VERSION = 4  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch, 4 velocity commands
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 CSRC_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 
@@ -73,6 +73,22 @@ def load_library(path: str | None = None) -> C.CDLL:
     for f in ("zb_create", "zb_destroy", "zb_reset", "zb_step", "zb_rollout", "zb_get_state", "zb_set_state",
               "zb_get_rand", "zb_set_rand", "zb_get_stats", "zb_get_solver_iters", "zb_debug_forward",
               "zb_set_step_chunks", "zb_mark_rollout_start", "zb_feet_airtime_exact", "zb_check"):
+        getattr(L, f).restype = C.c_int
+    # velocity commands (include/zbot_command.h) and their host twins
+    pc = C.POINTER(cs.ZbCommandConfig)
+    L.zb_command_config_struct_bytes.restype = C.c_size_t
+    L.zb_default_command_config.argtypes = [pc]
+    L.zb_default_command_config.restype = None
+    L.zb_command_config_check.argtypes = [pc]
+    L.zb_set_command_config.argtypes = [vp, pc]
+    L.zb_set_commands.argtypes = [vp, vp, vp, vp]
+    L.zb_get_commands.argtypes = [vp, vp, vp]
+    L.zb_get_command_terms.argtypes = [vp, vp, vp]
+    L.zb_command_initial_host.argtypes = [pc, C.c_uint64, vp, vp, vp, C.c_float, C.c_int, vp]
+    L.zb_command_next_host.argtypes = [pc, C.c_uint64, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
+    L.zb_command_rewards_host.argtypes = [pc, vp, vp, vp, vp, C.c_int, vp]
+    for f in ("zb_command_config_check", "zb_set_command_config", "zb_set_commands", "zb_get_commands",
+              "zb_get_command_terms", "zb_command_initial_host", "zb_command_next_host", "zb_command_rewards_host"):
         getattr(L, f).restype = C.c_int
     # post-rollout PPO inputs (include/zbot_ppo.h)
     L.zb_gae_partials_words.argtypes = [C.c_int]
@@ -139,6 +155,8 @@ def load_library(path: str | None = None) -> C.CDLL:
         raise ZbError("ZbModel layout mismatch between cstructs.py and the library")
     if L.zb_config_struct_bytes() != C.sizeof(cs.ZbEnvConfig):
         raise ZbError("ZbEnvConfig layout mismatch between cstructs.py and the library")
+    if L.zb_command_config_struct_bytes() != C.sizeof(cs.ZbCommandConfig):
+        raise ZbError("ZbCommandConfig layout mismatch between cstructs.py and the library")
     if path is None:
         _lib = L
     return L
@@ -160,6 +178,64 @@ def bank_cap(model) -> int:
     its ZbModel."""
     cm = model.cmodel if hasattr(model, "cmodel") else model
     return int(load_library().zb_bank_cap(C.byref(cm)))
+
+
+def _np_ptr(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def command_initial_host(ccfg: cs.ZbCommandConfig, seed: int, env, counter, quat, ctrl_dt: float):
+    """zb_command_initial_host: the initial commands [n, 7] of global envs `env` [n] at episode
+    counters `counter` [n] and base quaternions `quat` [n, 4] (numpy; needs no GPU)."""
+    import numpy as np  # noqa: PLC0415
+
+    env = np.ascontiguousarray(env, np.uint32)
+    counter = np.ascontiguousarray(counter, np.uint32)
+    quat = np.ascontiguousarray(quat, np.float32)
+    n = env.shape[0]
+    if counter.shape != (n,) or quat.shape != (n, 4):
+        raise ZbError("env [n], counter [n] and quat [n, 4] must agree")
+    out = np.empty((n, cs.CMD_WORDS), np.float32)
+    _check(load_library().zb_command_initial_host(C.byref(ccfg), seed, _np_ptr(env), _np_ptr(counter), _np_ptr(quat),
+                                                  float(ctrl_dt), n, _np_ptr(out)))
+    return out
+
+
+def command_next_host(ccfg: cs.ZbCommandConfig, seed: int, env, counter, prev, quat, ctrl_dt: float):
+    """zb_command_next_host: (next commands [n, 7], switched [n] uint8) from the commands `prev`
+    [n, 7] at step counters `counter` (rng_step) and post-step base quaternions `quat`."""
+    import numpy as np  # noqa: PLC0415
+
+    env = np.ascontiguousarray(env, np.uint32)
+    counter = np.ascontiguousarray(counter, np.uint32)
+    prev = np.ascontiguousarray(prev, np.float32)
+    quat = np.ascontiguousarray(quat, np.float32)
+    n = env.shape[0]
+    if counter.shape != (n,) or quat.shape != (n, 4) or prev.shape != (n, cs.CMD_WORDS):
+        raise ZbError("env [n], counter [n], prev [n, 7] and quat [n, 4] must agree")
+    out = np.empty((n, cs.CMD_WORDS), np.float32)
+    sw = np.empty(n, np.uint8)
+    _check(load_library().zb_command_next_host(C.byref(ccfg), seed, _np_ptr(env), _np_ptr(counter), _np_ptr(prev),
+                                               _np_ptr(quat), float(ctrl_dt), n, _np_ptr(out), _np_ptr(sw)))
+    return out, sw
+
+
+def command_rewards_host(ccfg: cs.ZbCommandConfig, cmd, quat, vel, height):
+    """zb_command_rewards_host: the five unscaled tracking terms [n, 5] of commands `cmd` [n, 7] on
+    body 1's xquat [n, 4], qvel[0:3] [n, 3] and xpos[1].z [n]."""
+    import numpy as np  # noqa: PLC0415
+
+    cmd = np.ascontiguousarray(cmd, np.float32)
+    quat = np.ascontiguousarray(quat, np.float32)
+    vel = np.ascontiguousarray(vel, np.float32)
+    height = np.ascontiguousarray(height, np.float32)
+    n = cmd.shape[0]
+    if cmd.shape != (n, cs.CMD_WORDS) or quat.shape != (n, 4) or vel.shape != (n, 3) or height.shape != (n,):
+        raise ZbError("cmd [n, 7], quat [n, 4], vel [n, 3] and height [n] must agree")
+    out = np.empty((n, cs.NUM_CMD_TERMS), np.float32)
+    _check(load_library().zb_command_rewards_host(C.byref(ccfg), _np_ptr(cmd), _np_ptr(quat), _np_ptr(vel),
+                                                  _np_ptr(height), n, _np_ptr(out)))
+    return out
 
 
 DBG_STRIDE = 1760
@@ -212,6 +288,7 @@ class HipEngine:
         self.reward = torch.zeros(n_envs, **f32)
         self.done = torch.zeros(n_envs, dtype=torch.uint8, device=self.device)
         self.success = torch.zeros(n_envs, dtype=torch.uint8, device=self.device)
+        self.command_cfg = None  # set_command_config
 
     def __del__(self):
         h = getattr(self, "h", None)
@@ -331,6 +408,35 @@ class HipEngine:
         DESIGN.md §4e). The same bits for every k."""
         _check(self.L.zb_set_step_chunks(self.h, int(k)))
 
+    def set_command_config(self, ccfg: cs.ZbCommandConfig | None) -> None:
+        """Velocity commands on (a config.command_config(...)) or off (None); zb_set_command_config.
+        Takes effect at the next reset() or step(); it does not resample by itself."""
+        _check(self.L.zb_set_command_config(self.h, None if ccfg is None else C.byref(ccfg)))
+        self.command_cfg = ccfg
+
+    def set_commands(self, cmd, mask=None) -> None:
+        """Overwrite the commands [n, 7] = [vx, vy, wz, heading, bh, rx, ry] of the envs `mask`
+        selects (None: all): the joystick override (zb_set_commands)."""
+        c = cmd.to(device=self.device, dtype=self.torch.float32).contiguous()
+        if tuple(c.shape) != (self.n, cs.CMD_WORDS):
+            raise ZbError(f"commands must be [{self.n}, {cs.CMD_WORDS}], got {tuple(c.shape)}")
+        m = None if mask is None else mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
+        if m is not None and tuple(m.shape) != (self.n,):
+            raise ZbError(f"mask must be [{self.n}], got {tuple(m.shape)}")
+        _check(self.L.zb_set_commands(self.h, _ptr(c), _ptr(m), self._stream()))
+        self.torch.cuda.current_stream(self.device).synchronize()
+
+    def get_commands(self):
+        out = self.torch.empty(self.n, cs.CMD_WORDS, dtype=self.torch.float32, device=self.device)
+        _check(self.L.zb_get_commands(self.h, _ptr(out), self._stream()))
+        return out
+
+    def get_command_terms(self):
+        """The five unscaled tracking terms [n, 5] of the last step (cs.CMD_TERM_NAMES order)."""
+        out = self.torch.empty(self.n, cs.NUM_CMD_TERMS, dtype=self.torch.float32, device=self.device)
+        _check(self.L.zb_get_command_terms(self.h, _ptr(out), self._stream()))
+        return out
+
     def check(self) -> None:
         """Synchronise and raise ZbError if a launch since the last check flagged its results
         invalid (zb_check: a chunked step's bounded hand-off wait timed out)."""
@@ -417,6 +523,7 @@ class EnvGroups:
             e.set_step_chunks(chunks)
         e0 = self.engines[0]
         self.L, self.device, self.cfg, self.seed = e0.L, e0.device, cfg, seed
+        self.command_cfg = None  # set_command_config
         for name in self.OUTPUTS:
             t = getattr(e0, name)
             full = torch.zeros((n_envs,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device)
@@ -560,6 +667,24 @@ class EnvGroups:
 
     def solver_iters(self):
         return self.torch.cat(self._each(lambda e, lo, hi: e.solver_iters()))
+
+    def set_command_config(self, ccfg) -> None:
+        """HipEngine.set_command_config for every group."""
+        self._each(lambda e, lo, hi: e.set_command_config(ccfg))
+        self.command_cfg = ccfg
+
+    def set_commands(self, cmd, mask=None) -> None:
+        c = cmd.to(device=self.device, dtype=self.torch.float32).contiguous()
+        if tuple(c.shape) != (self.n, cs.CMD_WORDS):
+            raise ZbError(f"commands must be [{self.n}, {cs.CMD_WORDS}], got {tuple(c.shape)}")
+        m = None if mask is None else mask.to(device=self.device, dtype=self.torch.uint8).contiguous()
+        self._each(lambda e, lo, hi: e.set_commands(c[lo:hi], None if m is None else m[lo:hi]))
+
+    def get_commands(self):
+        return self.torch.cat(self._each(lambda e, lo, hi: e.get_commands()))
+
+    def get_command_terms(self):
+        return self.torch.cat(self._each(lambda e, lo, hi: e.get_command_terms()))
 
     def check(self) -> None:
         self._each(lambda e, lo, hi: e.check())

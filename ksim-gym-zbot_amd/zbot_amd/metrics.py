@@ -26,3 +26,13 @@ def bytes_per_env_step(extras: bool = False, terms: bool = True, stats: bool = T
     if stats:
         b += 2 * cs.NUM_STATS * f + 4  # stats read+write, solver-iteration counter
     return b
+
+
+def command_term_means(terms) -> dict:
+    """Per-term means over the envs of the unscaled tracking terms [n, 5] of a step
+    (engine.get_command_terms(); include/zbot_command.h), under the names of cs.CMD_TERM_NAMES:
+    0-d tensors on the terms' device, nothing synchronised."""
+    if terms.dim() != 2 or terms.shape[1] != cs.NUM_CMD_TERMS:
+        raise ValueError(f"terms must be [n, {cs.NUM_CMD_TERMS}], got {tuple(terms.shape)}")
+    m = terms.double().mean(0)
+    return {name: m[i] for i, name in enumerate(cs.CMD_TERM_NAMES)}

@@ -19,7 +19,7 @@ from __future__ import annotations
 
 from . import cstructs as cs
 from .config import default_config
-from .constants import JOINT_BIASES, REWARDS
+from .constants import COMMAND_NAME, JOINT_BIASES, REWARDS
 from .curriculum import EpisodeLengthCurriculum, rollout_episode_length
 from .engine import EnvGroups, HipEngine
 from .model import compile_model
@@ -90,11 +90,12 @@ class StepResult:
     any stream context (e.g. `with torch.cuda.stream(side)`) sees the outputs complete on that stream.
     It is not a dataclass (reads are properties); as_dict() gives the fields as a plain dict."""
 
-    FIELDS = ("obs", "actor_inputs", "critic_inputs", "reward", "reward_terms", "done", "success")
+    FIELDS = ("obs", "actor_inputs", "critic_inputs", "reward", "reward_terms", "done", "success", "commands")
 
-    def __init__(self, obs, actor_inputs, critic_inputs, reward, reward_terms, done, success=None, join=None):
+    def __init__(self, obs, actor_inputs, critic_inputs, reward, reward_terms, done, success=None, join=None,
+                 commands=None):
         self._v = dict(obs=obs, actor_inputs=actor_inputs, critic_inputs=critic_inputs, reward=reward,
-                       reward_terms=reward_terms, done=done, success=success)
+                       reward_terms=reward_terms, done=done, success=success, commands=commands)
         self._join = join
 
     def _get(self, k):
@@ -113,6 +114,8 @@ class StepResult:
     reward_terms = property(lambda self: self._get("reward_terms"))
     done = property(lambda self: self._get("done"))
     success = property(lambda self: self._get("success"))  # time-limit ends without a failure (ksim successes_t)
+    # ksim's trajectory.command: {COMMAND_NAME: [n, 7]} = [vx, vy, wz, heading, bh, rx, ry], the command the next action answers
+    commands = property(lambda self: self._get("commands"))
 
 
 def default_groups(num_envs: int) -> int:
@@ -139,7 +142,8 @@ class ZbotWalkingEnv:
 
     def __init__(self, num_envs: int = 512, *, seed: int = 0, device: int = 0, env_offset: int = 0,
                  push: bool = False, randomize: bool = False, obs_noise: bool = True, model=None,
-                 curriculum: EpisodeLengthCurriculum | None = None, groups: int | None = None, **cfg_kw):
+                 curriculum: EpisodeLengthCurriculum | None = None, groups: int | None = None, command=None,
+                 **cfg_kw):
         self.model = model or compile_model()
         self.cfg = default_config(push=push, randomize=randomize, obs_noise=obs_noise, **cfg_kw)
         self.groups = default_groups(num_envs) if groups is None else int(groups)
@@ -148,6 +152,9 @@ class ZbotWalkingEnv:
                                     device=device, seed=seed)
         else:
             self.engine = HipEngine(self.model, self.cfg, num_envs, env_offset=env_offset, device=device, seed=seed)
+        self.command = command  # a config.command_config(...): velocity commands on (include/zbot_command.h)
+        if command is not None:
+            self.engine.set_command_config(command)
         self.num_envs = num_envs
         self.curriculum = curriculum or EpisodeLengthCurriculum()
         self.curriculum_state = self.curriculum.initial_state()
@@ -164,6 +171,10 @@ class ZbotWalkingEnv:
         if with_reward:
             rt = out["reward_terms"]
             terms = {name: rt[:, i] for i, (name, _, _) in enumerate(REWARDS)}
+            if self.command is not None:
+                self.engine.join()
+                ct = self.engine.get_command_terms()
+                terms.update({name: ct[:, i] for i, name in enumerate(cs.CMD_TERM_NAMES)})
         return StepResult(
             obs=observation_dict(out),
             actor_inputs=out["obs_actor"],
@@ -173,6 +184,7 @@ class ZbotWalkingEnv:
             done=out["done"] if with_reward else None,
             success=out["success"] if with_reward else None,
             join=self.engine.join if self.groups > 1 else None,
+            commands={COMMAND_NAME: out["obs_critic"][:, _CRITIC["cmd_all"][0]:_CRITIC["cmd_all"][1]]},
         )
 
     def reset(self, mask=None) -> StepResult:

@@ -4,7 +4,7 @@ update in HIP, the episode-length curriculum.
 
     tr = Trainer(engine, actor, critic, rollout_steps=200, num_passes=4, batch_size=128,
                  seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, group=None,
-                 **learner_kw)
+                 command_config=None, **learner_kw)
     m = tr.step()            # one iteration; returns metrics
     sd = tr.state_dict(); tr.load_state_dict(sd)
 
@@ -33,9 +33,13 @@ One step(), in order:
 
 from __future__ import annotations
 
+import ctypes
+
+from . import cstructs as cs
 from . import ppo
 from .curriculum import CurriculumState, EpisodeLengthCurriculum, rollout_episode_length
 from .engine import ZbError
+from .metrics import command_term_means
 from .learner import DEFAULT_BATCH_SIZE, DEFAULT_NUM_PASSES, HipPpoLearner
 from .policy import ACTOR, GruPolicy, PolicyRollout
 
@@ -52,7 +56,10 @@ class Trainer:
     def __init__(self, engine, actor: GruPolicy, critic: GruPolicy, rollout_steps: int = DEFAULT_ROLLOUT_STEPS,
                  num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, seed: int = 0,
                  shuffle: bool = True, curriculum: EpisodeLengthCurriculum | None = None, ctrl_dt: float = 0.02,
-                 group=None, **learner_kw):
+                 group=None, command_config: cs.ZbCommandConfig | None = None, **learner_kw):
+        """command_config: a config.command_config(...): the engine samples velocity commands
+        (include/zbot_command.h) and adds the tracking terms to the reward; step() then reports
+        the per-term means. It is set on the engine here and is part of state_dict()."""
         if actor.kind != ACTOR or critic.kind == ACTOR:
             raise ZbError("Trainer(engine, actor, critic): an actor and a critic handle, in this order")
         if rollout_steps < 1 or num_passes < 1 or batch_size < 1:
@@ -74,6 +81,9 @@ class Trainer:
             agree(dict(seed=self.seed % (1 << 63), shuffle=int(self.shuffle), rollout_steps=self.T,
                        num_passes=self.num_passes, batch_size=self.batch_size, envs_per_rank=int(engine.n)),
                   f"Trainer over {self.world} ranks", group)
+        self.command_config = command_config
+        if command_config is not None:
+            engine.set_command_config(command_config)  # before the rollout's first reset draws the commands
         self.curriculum = EpisodeLengthCurriculum() if curriculum is None else curriculum
         self.cur_state = self.curriculum.initial_state()
         self.rollout = PolicyRollout(engine, actor, seed=self.seed, curriculum=self.cur_state.level)
@@ -95,7 +105,8 @@ class Trainer:
     def step(self) -> dict:
         """One training iteration. Returns {"iteration", "level" (the level the rollout ran at),
         "episode_length" (seconds, a float), "reward" (mean per env-step, over all ranks), "loss", "clip_fraction",
-        "approx_kl" ([optimizer steps] each), "sums" (HipPpoLearner.update's list)}; the tensors are
+        "approx_kl" ([optimizer steps] each), "sums" (HipPpoLearner.update's list), and with a command
+        config "command_terms" (metrics.command_term_means of the rollout's last step)}; the tensors are
         on the device and nothing but the episode length is synchronised."""
         torch = self.torch
         ro, T = self.rollout, self.T
@@ -134,7 +145,11 @@ class Trainer:
             tot = reduce_fixed_order(torch.stack([r.double().sum(), torch.tensor(float(r.numel()), dtype=torch.float64,
                                                                                device=r.device)]), group=self.group)
             reward = tot[0] / tot[1]
-        return dict(iteration=self.iteration, level=level, episode_length=length, reward=reward,
+        extra = {}
+        if self.command_config is not None:
+            # the rollout's last step, mean over this rank's envs (zbot_amd.metrics)
+            extra["command_terms"] = command_term_means(self.eng.get_command_terms())
+        return dict(iteration=self.iteration, level=level, episode_length=length, reward=reward, **extra,
                     loss=-s[:, 0] / s[:, 4] + s[:, 5] * 0.5 * s[:, 1] / s[:, 4], clip_fraction=s[:, 2] / s[:, 4],
                     approx_kl=s[:, 3] / s[:, 4], sums=sums)
 
@@ -158,7 +173,8 @@ class Trainer:
             params=dict(actor=self.actor.params_tensor(), critic=self.critic.params_tensor()),
             learner=None if self.learner.state is None else self.learner.state_dict(),
             curriculum=dict(level=float(self.cur_state.level), steps=int(self.cur_state.steps)),
-            iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle, world=self.world, rank=self.rank)
+            iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle, world=self.world, rank=self.rank,
+            command_config=None if self.command_config is None else bytes(self.command_config))
 
     def load_state_dict(self, sd: dict) -> None:
         """Restore state_dict()'s result into this Trainer's engine, handles and learner."""
@@ -173,7 +189,12 @@ class Trainer:
         if int(sd.get("world", 1)) != self.world or int(sd.get("rank", 0)) != self.rank:
             raise ZbError(f"the state is rank {sd.get('rank', 0)}'s of {sd.get('world', 1)}; this Trainer is rank "
                           f"{self.rank} of {self.world}")
-        self.eng.set_state(e["state"])
+        cc = sd.get("command_config")
+        if cc is not None and len(cc) != ctypes.sizeof(cs.ZbCommandConfig):
+            raise ZbError(f"the state's command config has {len(cc)} bytes, ZbCommandConfig {ctypes.sizeof(cs.ZbCommandConfig)}")
+        self.command_config = None if cc is None else cs.ZbCommandConfig.from_buffer_copy(cc)
+        self.eng.set_command_config(self.command_config)
+        self.eng.set_state(e["state"])  # the commands are words of the state rows
         self.eng.set_rand(e["rand"])
         ro, r = self.rollout, sd["rollout"]
         to = lambda t: None if t is None else t.to(dev).clone()  # noqa: E731
