@@ -3005,11 +3005,24 @@ __device__ __forceinline__ void make_constraints(const Ctx& c, const EnvS& s, co
 
 /* ------------------------------ Newton solver ------------------------------ */
 /* row cost / force / activity (mj_constraintUpdate), branch-free selects */
+/* SEL (solve_cg's default-fields copy): the cost's three zone values are computed on every lane, each
+   rounded where it stands, and selected. The nested ternaries alone compile to nested exec regions
+   (9 scalar instructions and two branches around 6 VALU), and the lanes of a wave sit in different
+   zones, so every arm runs anyway. Same three expressions, same selection: the same bits
+   (tests/test_gpu_slot_diet.py). The Newton copy keeps the ternaries: with the select form its
+   fixtures moved, so it is left off there. */
+template <bool SEL = false>
 __device__ __forceinline__ float eval_fric(float jar, float D, float R, float fl, float& force, int& act) {
   const float Rf = R * fl;
   const bool lo = jar <= -Rf, hi = jar >= Rf;
   force = lo ? fl : (hi ? -fl : -D * jar);
   act = (lo || hi) ? 0 : 1;
+  if constexpr (SEL) {
+    const float klo = rounded(-fl * (0.5f * Rf + jar)), khi = rounded(fl * (jar - 0.5f * Rf));
+    const float klin = rounded(0.5f * D * jar * jar);
+    const float kout = hi ? khi : klin;
+    return lo ? klo : kout;
+  }
   return lo ? -fl * (0.5f * Rf + jar) : (hi ? fl * (jar - 0.5f * Rf) : 0.5f * D * jar * jar);
 }
 __device__ __forceinline__ float eval_one(float jar, float D, float& force, int& act) {
@@ -3020,13 +3033,13 @@ __device__ __forceinline__ float eval_one(float jar, float D, float& force, int&
 }
 
 /* row costs at given jar values (no state change); jx, jy, jz: the extra banks' contact rows (XG) */
-template <int XG, bool XA = true>
+template <int XG, bool XA = true, bool DS = false>
 __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc, float jf_, float jl_, float jx,
                                            float jy = 0.f, float jz = 0.f) {
   float f;
   int a;
   const float k0 = eval_one(jc, r.D, f, a);
-  const float k1 = eval_fric(jf_, r.Df, r.Rf, r.fl, f, a);
+  const float k1 = eval_fric<DS>(jf_, r.Df, r.Rf, r.fl, f, a);
   float cost = 0.f;
   cost += r.ex ? k0 : 0.f;
   cost += r.hf ? k1 : 0.f;
@@ -3123,7 +3136,7 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     float f0, f1;
     int a0, a1;
     const float k0 = eval_one(r.jar, r.D, f0, a0);
-    const float k1 = eval_fric(r.jf, r.Df, r.Rf, r.fl, f1, a1);
+    const float k1 = eval_fric<MD && ZL>(r.jf, r.Df, r.Rf, r.fl, f1, a1);
     if constexpr (ZL) {
       cost += k0;
       cost += k1;
@@ -3889,8 +3902,8 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     }
   }
   tsync();
-  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy, jwz),
-                  rows_cost<XG, XA>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy, jsz)};
+  float cws[2] = {(c.l < NV ? 0.5f * (Ma - fs) * (x - qs) : 0.f) + rows_cost<XG, XA, DS>(c, r, jw, x - r.af, r.sl * x - r.al, jwx, jwy, jwz),
+                  rows_cost<XG, XA, DS>(c, r, js, qs - r.af, r.sl * qs - r.al, jsx, jsy, jsz)};
   tsum_n<2>(cws);
   if (cws[0] > cws[1]) {
     x = qs;

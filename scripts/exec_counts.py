@@ -33,7 +33,7 @@ sys.path.insert(0, os.path.join(ROOT, "ksim-gym-zbot_amd"))
 
 NAMES = ["forward", "solve", "ls", "ls_ret0", "ls_limit", "eval", "eval_wave", "it_cap", "it_tol", "it_full",
          "prologue_cyc", "epilogue_cyc", "step"]
-KERNEL = "_ZN2zb11step_kernelILi1ELi0ELi0ELb1EEEvNS_8StepArgsE"
+KERNEL = "_ZN2zb11step_kernelILi1ELi0ELi0ELb1ELb0EEEvNS_8StepArgsE"
 NSLOTS = 20
 
 
