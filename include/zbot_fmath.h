@@ -259,4 +259,86 @@ ZBF_FN float zbf_mix_sample(const float* mu, const float* sd, const float* lg, i
   return mu[pick] + sd[pick] * z;
 }
 
+/* ---- the same head over nm components, 1 <= nm <= ZBF_MAX_MIX (shaped policy handles, zbot_policy.h) ----
+   The operations and their order are those of the two functions above with nm in place of ZBF_NMIX, so
+   at nm = 5 the results are the same bits. The loops run over the maximum with a guard, so that a GPU
+   compiler unrolls them and keeps mu / sd / lg and the locals in registers; the arrays passed in need
+   only their first nm entries set. */
+#define ZBF_MAX_MIX 8
+#if defined(__HIPCC__)
+#define ZBF_UNROLL _Pragma("unroll")
+#else
+#define ZBF_UNROLL
+#endif
+
+ZBF_FN float zbf_mix_log_prob_n(const float* mu, const float* sd, const float* lg, int nm, float a) {
+  float mx = lg[0];
+  ZBF_UNROLL
+  for (int m = 1; m < ZBF_MAX_MIX; m++)
+    if (m < nm) mx = lg[m] > mx ? lg[m] : mx;
+  float S = 0.0f;
+  ZBF_UNROLL
+  for (int m = 0; m < ZBF_MAX_MIX; m++)
+    if (m < nm) S = S + zbf_exp(lg[m] - mx);
+  const float logS = zbf_log(S);
+  float v[ZBF_MAX_MIX];
+  float M = -3.0e38f;
+  ZBF_UNROLL
+  for (int m = 0; m < ZBF_MAX_MIX; m++) {
+    v[m] = 0.0f;
+    if (m < nm) {
+      const float zm = (a - mu[m]) / sd[m];
+      const float lnm = ((-0.5f * zm) * zm - zbf_log(sd[m])) - ZBF_HALF_LOG_2PI;
+      v[m] = ((lg[m] - mx) - logS) + lnm;
+      M = v[m] > M ? v[m] : M;
+    }
+  }
+  float acc = 0.0f;
+  ZBF_UNROLL
+  for (int m = 0; m < ZBF_MAX_MIX; m++)
+    if (m < nm) acc = acc + zbf_exp(v[m] - M);
+  return M + zbf_log(acc);
+}
+
+ZBF_FN float zbf_mix_sample_n(const float* mu, const float* sd, const float* lg, int nm, int argmax, uint64_t seed,
+                              uint32_t purpose, uint32_t k_cat, uint32_t k_normal, uint32_t env, uint32_t step) {
+  float mx = lg[0];
+  float mu_am = mu[0];
+  ZBF_UNROLL
+  for (int m = 1; m < ZBF_MAX_MIX; m++)
+    if (m < nm && lg[m] > mx) {
+      mx = lg[m];
+      mu_am = mu[m];
+    }
+  if (argmax) return mu_am;
+  float e[ZBF_MAX_MIX];
+  float S = 0.0f;
+  ZBF_UNROLL
+  for (int m = 0; m < ZBF_MAX_MIX; m++) {
+    e[m] = 0.0f;
+    if (m < nm) {
+      e[m] = zbf_exp(lg[m] - mx);
+      S = S + e[m];
+    }
+  }
+  uint32_t a, b;
+  zbf_rng_bits(seed, purpose, k_cat, env, step, &a, &b);
+  const float target = zbf_u01(a) * S;
+  /* first m with target < c_m, as selects; the last component when there is none */
+  float mu_p = mu[0], sd_p = sd[0];
+  int found = 0;
+  float c = 0.0f;
+  ZBF_UNROLL
+  for (int m = 0; m < ZBF_MAX_MIX; m++)
+    if (m < nm) {
+      c = c + e[m];
+      const int take = !found && (target < c || m == nm - 1);
+      mu_p = take ? mu[m] : mu_p;
+      sd_p = take ? sd[m] : sd_p;
+      found = found || take;
+    }
+  const float z = zbf_normal(seed, purpose, k_normal, env, step);
+  return mu_p + sd_p * z;
+}
+
 #endif /* ZBOT_FMATH_H */

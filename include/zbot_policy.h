@@ -160,6 +160,70 @@ int zb_policy_actor_backward(ZbPolicy* p, const float* obs, int T, int n, const 
 int zb_policy_critic_backward(ZbPolicy* p, const float* obs, int T, int n, const float* carry0, const uint8_t* reset,
                               const float* d_value, float* scratch, size_t scratch_words, float* grad, void* stream);
 
+/*
+ * ---- Network shape: GRU depth and mixture count per handle ----
+ *
+ * train.py's config opens with hidden_size, depth and num_mixtures (train.py:1065-1076; Model, Actor and
+ * Critic take them, :898-944, :977-1013, :1604-1614). Everything above is the default shape (128, 5, 5).
+ * A shaped handle has D = depth GRU layers and, for the actor, O = 60 * num_mixtures outputs ordered
+ * means [20][m], stds [20][m], logits [20][m] (train.py:955-958); the critic has one output whatever
+ * num_mixtures is (it is range-checked for both kinds). The parameter layout is the one at the top of this
+ * file with these D and O: H I + H + D (6 H^2 + 4 H) + O H + O floats, plus 20 for the actor. The carry is
+ * [n][depth][128]. Every entry point above takes a shaped handle and means the same thing on it.
+ *
+ *   hidden_size  128 only. The wave count of a workgroup (H / 16), the gate-tile indices, the fragment
+ *                groups and every LDS tile are built on it; any other value is refused with ZB_EARG and
+ *                "hidden_size" in zb_last_error.
+ *   depth        1 .. ZB_POL_MAX_DEPTH, num_mixtures 1 .. ZB_POL_MAX_MIX; outside: ZB_EARG, field named.
+ *
+ * Kernels. A default-shape handle without ZB_POL_SHAPE_GENERIC launches exactly the kernels of
+ * zb_policy_create (compiled for depth 5 and 5 mixtures). Every other handle launches the shape-generic
+ * set: one instantiation per kernel form with depth and mixture count as runtime values bounded by the
+ * two maxima, the same k-ordered chains, epilogue order and reduction order, so at the default shape the
+ * two sets return the same bits (forward, training forward and gradient). The generic set exists in the
+ * 32-env block layout only, one-step and persistent: zb_policy_set_layout to a slot-sized layout
+ * (ZB_POL_LAYOUT_WAVE, _WAVE2, _WAVE4) on such a handle returns ZB_EARG, and such handles ignore the
+ * environment's ZB_POLICY_LAYOUT. Their persistent form keeps the carries in memory between steps (each
+ * thread reads back the 8 values per layer it wrote), not in registers.
+ *
+ * Training scratch of a shaped handle: the planes of the default layout with D layers and a raw-head row
+ * stride of 60 m rounded up to 16, plus one [D][n][128] plane for the time-direction gradient that the
+ * default kernel keeps in registers. Use zb_policy_train_scratch_words_shaped (a flagged default shape
+ * needs more words than zb_policy_train_scratch_words says). The reduction order of the parameter
+ * gradient is the one above at every shape.
+ */
+#define ZB_POL_MAX_DEPTH 8
+#define ZB_POL_MAX_MIX 8
+#define ZB_POL_SHAPE_GENERIC 1u /* flags: run the shape-generic kernels even at the default shape */
+typedef struct ZbPolicyShape {
+  int32_t struct_bytes;  /* sizeof(ZbPolicyShape) */
+  int32_t hidden_size;   /* 128 */
+  int32_t depth;         /* 1..ZB_POL_MAX_DEPTH */
+  int32_t num_mixtures;  /* 1..ZB_POL_MAX_MIX; read for the actor, range-checked for both */
+  uint32_t flags;        /* ZB_POL_SHAPE_GENERIC or 0 */
+} ZbPolicyShape;
+
+/* 128, 5, 5, flags 0 */
+void zb_policy_default_shape(ZbPolicyShape* shape);
+/* parameters of a (kind, shape) network; 0 on a bad kind or shape (zb_last_error names the field) */
+size_t zb_policy_param_count_shaped(int kind, const ZbPolicyShape* shape);
+/* zb_policy_create with a shape; zb_policy_create is this with zb_policy_default_shape */
+int zb_policy_create_shaped(int kind, const ZbPolicyShape* shape, const float* params, size_t n_params, int device,
+                            ZbPolicy** out);
+int zb_policy_get_shape(const ZbPolicy* p, ZbPolicyShape* shape);
+/* scratch words of a shaped handle's training calls (0 on a bad argument) */
+size_t zb_policy_train_scratch_words_shaped(int kind, const ZbPolicyShape* shape, int T, int n);
+
+/* Host twins: zb_policy_actor / zb_policy_critic on the CPU, every pointer a host pointer. They are the
+ * bit reference of the kernels at every shape: each product the k-ordered fp32 fmaf chain from 0, biases
+ * and the GRU update in the kernels' order without contraction, zbot_fmath.h functions and RNG. The
+ * backward pass has no host twin (its reference is fp64 autograd). */
+int zb_policy_actor_host(const ZbPolicyShape* shape, const float* params, const float* obs, int T, int n, float* carry,
+                         const uint8_t* reset, int mode, uint64_t seed, int env_offset, uint32_t step0, float* actions,
+                         float* log_prob);
+int zb_policy_critic_host(const ZbPolicyShape* shape, const float* params, const float* obs, int T, int n, float* carry,
+                          const uint8_t* reset, float* value);
+
 #ifdef __cplusplus
 }
 #endif

@@ -608,14 +608,20 @@ struct ZbPolicy {
   size_t wpack_words, wpack_t_words, bias_words;
   int layout; /* ZB_POL_LAYOUT_* */
   int persistent; /* block layout: one launch per call over all T steps */
+  int depth, nmix; /* the handle's shape (include/zbot_policy.h "Network shape") */
+  int generic;     /* 1: the shape-generic kernels (any shape but the default, or ZB_POL_SHAPE_GENERIC) */
+  size_t n_params;
 };
 
 static int pol_in(int kind) { return kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN; }
-static int pol_out(int kind) { return kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_OUT : 1; }
+static int pol_out(int kind, int nmix) { return kind == ZB_POL_ACTOR ? 3 * ZB_POL_JOINTS * nmix : 1; }
+static zb::TrainLayout pol_train_layout(const ZbPolicy* h, int T, int n) {
+  return h->generic ? zb::train_layout_shaped(h->kind, h->depth, h->nmix, T, n) : zb::train_layout(h->kind, T, n);
+}
 
 size_t zb_policy_param_count(int kind) {
   if (kind != ZB_POL_ACTOR && kind != ZB_POL_CRITIC) return 0;
-  const size_t H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH, I = (size_t)pol_in(kind), O = (size_t)pol_out(kind);
+  const size_t H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH, I = (size_t)pol_in(kind), O = (size_t)pol_out(kind, ZB_POL_MIX);
   return H * I + H + D * (6 * H * H + 4 * H) + O * H + O + (kind == ZB_POL_ACTOR ? ZB_POL_JOINTS : 0);
 }
 
@@ -642,12 +648,21 @@ static void pack_bt(const float* W, int K, int N, std::vector<float>& out) {
 }
 
 int zb_policy_create(int kind, const float* params, size_t n_params, int device, ZbPolicy** out) {
+  ZbPolicyShape shape;
+  zb_policy_default_shape(&shape);
+  return zb_policy_create_shaped(kind, &shape, params, n_params, device, out);
+}
+
+int zb_policy_create_shaped(int kind, const ZbPolicyShape* shape, const float* params, size_t n_params, int device,
+                            ZbPolicy** out) {
   if (!out || !params) return fail(ZB_EARG, "zb_policy_create: null argument");
   *out = nullptr;
-  if (kind != ZB_POL_ACTOR && kind != ZB_POL_CRITIC) return fail(ZB_EARG, "zb_policy_create: unknown kind %d", kind);
-  const size_t need = zb_policy_param_count(kind);
+  if (int rc = zb::check_policy_shape("zb_policy_create", kind, shape)) return rc;
+  const size_t need = zb_policy_param_count_shaped(kind, shape);
   if (n_params != need) return fail(ZB_EARG, "zb_policy_create: %zu parameters, expected %zu", n_params, need);
-  const int H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH, I = pol_in(kind), O = pol_out(kind);
+  const int H = ZB_POL_HIDDEN, D = shape->depth, I = pol_in(kind), O = pol_out(kind, shape->num_mixtures);
+  const bool generic = (shape->flags & ZB_POL_SHAPE_GENERIC) || D != ZB_POL_DEPTH ||
+                       (kind == ZB_POL_ACTOR && shape->num_mixtures != ZB_POL_MIX);
   std::vector<float> wp, bias, wt;
   const float* p = params;
   pack_b(p, H, I, wp); /* input_proj.weight */
@@ -681,9 +696,14 @@ int zb_policy_create(int kind, const float* params, size_t n_params, int device,
   HIPCHK(hipSetDevice(device));
   ZbPolicy* h = new ZbPolicy();
   h->kind = kind;
+  h->depth = D;
+  h->nmix = shape->num_mixtures;
+  h->generic = generic ? 1 : 0;
+  h->n_params = need;
   {
+    /* the shape-generic kernels exist in the block layout only: such handles ignore the variable */
     const char* lay = getenv("ZB_POLICY_LAYOUT");
-    h->layout = (lay && lay[0] == 'w') ? ZB_POL_LAYOUT_WAVE : ZB_POL_LAYOUT_BLOCK;
+    h->layout = (!generic && lay && lay[0] == 'w') ? ZB_POL_LAYOUT_WAVE : ZB_POL_LAYOUT_BLOCK;
   }
   h->persistent = 1;
   h->device = device;
@@ -739,7 +759,7 @@ static int policy_run(ZbPolicy* h, int kind, const float* obs, int T, int n, flo
      zb_policy.hip); the slot-sized layouts launch once per step */
   const int per_launch = (h->layout == ZB_POL_LAYOUT_BLOCK && h->persistent) ? T : 1;
   for (int t = 0; t < T; t += per_launch) {
-    zb::PolicyArgs a;
+    zb::PolicyArgsG a;
     memset(&a, 0, sizeof a);
     a.obs = obs + (size_t)t * n * I;
     a.carry = carry;
@@ -756,6 +776,7 @@ static int policy_run(ZbPolicy* h, int kind, const float* obs, int T, int n, flo
     a.bias = h->bias;
     a.layout = h->layout;
     a.T = per_launch;
+    a.generic = h->generic, a.depth = h->depth, a.nmix = h->nmix;
     hipError_t e = zb::launch_policy(kind, a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(ZB_ELAUNCH, "policy launch: %s", hipGetErrorString(e));
   }
@@ -773,6 +794,9 @@ int zb_policy_set_layout(ZbPolicy* p, int layout) {
   if (layout != ZB_POL_LAYOUT_BLOCK && layout != ZB_POL_LAYOUT_WAVE && layout != ZB_POL_LAYOUT_WAVE2 &&
       layout != ZB_POL_LAYOUT_WAVE4)
     return fail(ZB_EARG, "unknown layout %d", layout);
+  if (p->generic && layout != ZB_POL_LAYOUT_BLOCK)
+    return fail(ZB_EARG, "zb_policy_set_layout: the shape-generic kernels (depth %d, %d mixtures%s) run the block "
+                "layout only", p->depth, p->nmix, p->depth == ZB_POL_DEPTH && p->nmix == ZB_POL_MIX ? ", flagged" : "");
   p->layout = layout;
   return ZB_OK;
 }
@@ -796,14 +820,33 @@ size_t zb_policy_train_scratch_words(int kind, int T, int n) {
   return zb::train_layout(kind, T, n).total;
 }
 
+size_t zb_policy_train_scratch_words_shaped(int kind, const ZbPolicyShape* shape, int T, int n) {
+  if (zb::check_policy_shape("zb_policy_train_scratch_words_shaped", kind, shape) != ZB_OK) return 0;
+  if (T <= 0 || n <= 0) return 0;
+  const bool generic = (shape->flags & ZB_POL_SHAPE_GENERIC) || shape->depth != ZB_POL_DEPTH ||
+                       (kind == ZB_POL_ACTOR && shape->num_mixtures != ZB_POL_MIX);
+  return generic ? zb::train_layout_shaped(kind, shape->depth, shape->num_mixtures, T, n).total
+                 : zb::train_layout(kind, T, n).total;
+}
+
+int zb_policy_get_shape(const ZbPolicy* p, ZbPolicyShape* shape) {
+  if (!p || !shape) return fail(ZB_EARG, "zb_policy_get_shape: null argument");
+  zb_policy_default_shape(shape);
+  shape->depth = p->depth;
+  shape->num_mixtures = p->nmix;
+  /* set for every handle that runs the shape-generic kernels, so that the shape sizes its scratch */
+  shape->flags = p->generic ? ZB_POL_SHAPE_GENERIC : 0;
+  return ZB_OK;
+}
+
 int zb_policy_set_params(ZbPolicy* h, const float* params, size_t n_params, void* stream) {
   if (!h || !params) return fail(ZB_EARG, "zb_policy_set_params: null argument");
-  const size_t need = zb_policy_param_count(h->kind);
+  const size_t need = h->n_params;
   if (n_params != need) return fail(ZB_EARG, "zb_policy_set_params: %zu parameters, expected %zu", n_params, need);
   int cur = -1;
   HIPCHK(hipGetDevice(&cur));
   if (cur != h->device) HIPCHK(hipSetDevice(h->device));
-  hipError_t e = zb::launch_policy_pack(h->kind, params, h->wpack, h->wpack_t, h->bias, (hipStream_t)stream);
+  hipError_t e = zb::launch_policy_pack(h->kind, h->depth, h->nmix, params, h->wpack, h->wpack_t, h->bias, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_policy_set_params: %s", hipGetErrorString(e));
   return ZB_OK;
 }
@@ -820,7 +863,7 @@ static int train_check(ZbPolicy* h, int kind, const float* obs, int T, int n, co
     return fail(ZB_EARG, "%s: T n = %llu rows exceed 2^31 - 1", what, (unsigned long long)T * n);
   if (!obs || !carry0 || !a || !b || !scratch) return fail(ZB_EARG, "%s: null pointer", what);
   if ((uintptr_t)carry0 % 16) return fail(ZB_EARG, "%s: carry0 must be 16-byte aligned", what);
-  const size_t need = zb::train_layout(kind, T, n).total;
+  const size_t need = pol_train_layout(h, T, n).total;
   if (scratch_words < need)
     return fail(ZB_EARG, "%s: scratch of %zu words, (T=%d, n=%d) needs %zu", what, scratch_words, T, n, need);
   int cur = -1;
@@ -837,7 +880,7 @@ static int train_forward(ZbPolicy* h, int kind, const float* obs, int T, int n, 
                              kind == ZB_POL_ACTOR ? (const void*)log_prob : (const void*)value, scratch, scratch_words,
                              what);
   if (rc != ZB_OK) return rc == 1 ? ZB_OK : rc;
-  zb::PolicyArgs a;
+  zb::PolicyArgsG a;
   memset(&a, 0, sizeof a);
   a.obs = obs;
   a.carry = const_cast<float*>(carry0); /* read-only in the SAVE kernels */
@@ -852,6 +895,7 @@ static int train_forward(ZbPolicy* h, int kind, const float* obs, int T, int n, 
   a.layout = ZB_POL_LAYOUT_BLOCK;
   a.T = T;
   a.save = scratch;
+  a.generic = h->generic, a.depth = h->depth, a.nmix = h->nmix;
   hipError_t e = zb::launch_policy(kind, a, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
   return ZB_OK;
@@ -865,12 +909,12 @@ static int train_backward(ZbPolicy* h, int kind, const float* obs, int T, int n,
   const int rc = train_check(h, kind, obs, T, n, carry0, kind == ZB_POL_ACTOR ? (const void*)actions : (const void*)dout,
                              dout, scratch, scratch_words, what);
   if (rc == 1) {
-    hipError_t e = hipMemsetAsync(grad, 0, zb_policy_param_count(kind) * sizeof(float), (hipStream_t)stream);
+    hipError_t e = hipMemsetAsync(grad, 0, h->n_params * sizeof(float), (hipStream_t)stream);
     if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
     return ZB_OK;
   }
   if (rc != ZB_OK) return rc;
-  zb::PolicyBwdArgs a;
+  zb::PolicyBwdArgsG a;
   memset(&a, 0, sizeof a);
   a.obs = obs;
   a.reset = reset;
@@ -882,6 +926,7 @@ static int train_backward(ZbPolicy* h, int kind, const float* obs, int T, int n,
   a.bias = h->bias;
   a.T = T;
   a.n = n;
+  a.generic = h->generic, a.depth = h->depth, a.nmix = h->nmix;
   hipError_t e = zb::launch_policy_backward(kind, a, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s: %s", what, hipGetErrorString(e));
   return ZB_OK;

@@ -505,6 +505,23 @@ static double tree_root(const Leaf& leaf, size_t count) {
   return tree_sum(leaf, 0, len, count) + 0.0;
 }
 
+int check_policy_shape(const char* what, int kind, const ZbPolicyShape* s) {
+  if (kind != ZB_POL_ACTOR && kind != ZB_POL_CRITIC) return fail(ZB_EARG, "%s: unknown kind %d", what, kind);
+  if (!s) return fail(ZB_EARG, "%s: null shape", what);
+  if (s->struct_bytes != (int32_t)sizeof(ZbPolicyShape))
+    return fail(ZB_EARG, "%s: struct_bytes %d, this library's ZbPolicyShape has %zu", what, s->struct_bytes,
+                sizeof(ZbPolicyShape));
+  if (s->hidden_size != ZB_POL_HIDDEN)
+    return fail(ZB_EARG, "%s: hidden_size %d: only %d is built (the workgroup and every LDS tile are sized on it)",
+                what, s->hidden_size, ZB_POL_HIDDEN);
+  if (s->depth < 1 || s->depth > ZB_POL_MAX_DEPTH)
+    return fail(ZB_EARG, "%s: depth %d outside 1..%d", what, s->depth, ZB_POL_MAX_DEPTH);
+  if (s->num_mixtures < 1 || s->num_mixtures > ZB_POL_MAX_MIX)
+    return fail(ZB_EARG, "%s: num_mixtures %d outside 1..%d", what, s->num_mixtures, ZB_POL_MAX_MIX);
+  if (s->flags & ~ZB_POL_SHAPE_GENERIC) return fail(ZB_EARG, "%s: unknown flags 0x%x", what, s->flags);
+  return ZB_OK;
+}
+
 }  // namespace zb
 
 using zb::fail;
@@ -601,6 +618,150 @@ static void command_uniforms(uint64_t seed, uint32_t k0, uint32_t env, uint32_t 
 size_t zb_command_config_struct_bytes(void) { return sizeof(ZbCommandConfig); }
 
 int zb_command_config_check(const ZbCommandConfig* cfg) { return zb::check_command_config(cfg); }
+
+/* ---- shaped policy handles: the shape's checks and the host twins of the forward kernels (zb_policy.hip) ---- */
+
+void zb_policy_default_shape(ZbPolicyShape* s) {
+  if (!s) return;
+  s->struct_bytes = (int32_t)sizeof(ZbPolicyShape);
+  s->hidden_size = ZB_POL_HIDDEN;
+  s->depth = ZB_POL_DEPTH;
+  s->num_mixtures = ZB_POL_MIX;
+  s->flags = 0;
+}
+
+size_t zb_policy_param_count_shaped(int kind, const ZbPolicyShape* s) {
+  if (zb::check_policy_shape("zb_policy_param_count_shaped", kind, s) != ZB_OK) return 0;
+  const size_t H = ZB_POL_HIDDEN, D = (size_t)s->depth;
+  const size_t I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN;
+  const size_t O = kind == ZB_POL_ACTOR ? (size_t)3 * ZB_POL_JOINTS * (size_t)s->num_mixtures : 1;
+  return H * I + H + D * (6 * H * H + 4 * H) + O * H + O + (kind == ZB_POL_ACTOR ? ZB_POL_JOINTS : 0);
+}
+
+namespace {
+
+struct PolNet {
+  const float *win, *bin, *wih[ZB_POL_MAX_DEPTH], *whh[ZB_POL_MAX_DEPTH], *b[ZB_POL_MAX_DEPTH], *bn[ZB_POL_MAX_DEPTH];
+  const float *wout, *bout, *mean_bias;
+  int I, O, D, nm;
+};
+
+PolNet pol_net(const float* P, int kind, const ZbPolicyShape* s) {
+  constexpr int H = ZB_POL_HIDDEN;
+  PolNet n;
+  n.I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN;
+  n.D = s->depth;
+  n.nm = s->num_mixtures;
+  n.O = kind == ZB_POL_ACTOR ? 3 * ZB_POL_JOINTS * n.nm : 1;
+  const float* p = P;
+  n.win = p, p += (size_t)H * n.I;
+  n.bin = p, p += H;
+  for (int l = 0; l < n.D; l++) {
+    n.wih[l] = p, p += (size_t)3 * H * H;
+    n.whh[l] = p, p += (size_t)3 * H * H;
+    n.b[l] = p, p += 3 * H;
+    n.bn[l] = p, p += H;
+  }
+  n.wout = p, p += (size_t)n.O * H;
+  n.bout = p, p += n.O;
+  n.mean_bias = kind == ZB_POL_ACTOR ? p : nullptr;
+  return n;
+}
+
+/* the matrix cores' chain: from 0, k ascending, one fmaf a step */
+float pol_dot(const float* x, const float* w, int K) {
+  float acc = 0.0f;
+  for (int k = 0; k < K; k++) acc = fmaf(x[k], w[k], acc);
+  return acc;
+}
+
+/* one env, one step, in policy_kernel's order: (chain + bias) for the input gates, the bare chain for the
+   hidden gates, r / z from (ig + b) + hg, n from (ig + b) + r (hg + b_n), h' = n + z (h - n); carry [D][H]
+   updated in place, out [O] = chain + bias */
+void pol_forward(const PolNet& nt, const float* obs, float* carry, float* out) {
+  constexpr int H = ZB_POL_HIDDEN;
+  float x[H], xn[H];
+  for (int u = 0; u < H; u++) x[u] = pol_dot(obs, nt.win + (size_t)u * nt.I, nt.I) + nt.bin[u];
+  for (int l = 0; l < nt.D; l++) {
+    float* h = carry + (size_t)l * H;
+    for (int u = 0; u < H; u++) {
+      float ig[3], hg[3];
+      for (int g = 0; g < 3; g++) {
+        ig[g] = pol_dot(x, nt.wih[l] + (size_t)(g * H + u) * H, H) + nt.b[l][g * H + u];
+        hg[g] = pol_dot(h, nt.whh[l] + (size_t)(g * H + u) * H, H);
+      }
+      const float r = zbf_sigmoid(ig[0] + hg[0]);
+      const float z = zbf_sigmoid(ig[1] + hg[1]);
+      const float nn = zbf_tanh(ig[2] + r * (hg[2] + nt.bn[l][u]));
+      xn[u] = nn + z * (h[u] - nn);
+    }
+    memcpy(h, xn, sizeof xn);
+    memcpy(x, xn, sizeof xn);
+  }
+  for (int c = 0; c < nt.O; c++) out[c] = pol_dot(x, nt.wout + (size_t)c * H, H) + nt.bout[c];
+}
+
+int pol_host_check(const char* what, int kind, const ZbPolicyShape* s, const float* params, const float* obs, int T,
+                   int n, const float* carry, int env_offset) {
+  if (int rc = zb::check_policy_shape(what, kind, s)) return rc;
+  if (T < 0 || n < 0 || env_offset < 0) return fail(ZB_EARG, "%s: bad size (T=%d n=%d offset=%d)", what, T, n, env_offset);
+  if (T == 0 || n == 0) return 1;
+  if (!params || !obs || !carry) return fail(ZB_EARG, "%s: null params, obs or carry", what);
+  return ZB_OK;
+}
+
+}  // namespace
+
+int zb_policy_actor_host(const ZbPolicyShape* s, const float* params, const float* obs, int T, int n, float* carry,
+                         const uint8_t* reset, int mode, uint64_t seed, int env_offset, uint32_t step0, float* actions,
+                         float* log_prob) {
+  const int rc = pol_host_check("zb_policy_actor_host", ZB_POL_ACTOR, s, params, obs, T, n, carry, env_offset);
+  if (rc != ZB_OK) return rc == 1 ? ZB_OK : rc;
+  if (!actions) return fail(ZB_EARG, "zb_policy_actor_host: null actions");
+  if (mode != ZB_POL_SAMPLE && mode != ZB_POL_MODE && mode != ZB_POL_EVAL)
+    return fail(ZB_EARG, "zb_policy_actor_host: unknown mode %d", mode);
+  constexpr int H = ZB_POL_HIDDEN, NJ = ZB_POL_JOINTS;
+  const PolNet nt = pol_net(params, ZB_POL_ACTOR, s);
+  const int nm = nt.nm;
+  std::vector<float> out((size_t)nt.O);
+  for (int t = 0; t < T; t++)
+    for (int e = 0; e < n; e++) {
+      float* ce = carry + (size_t)e * nt.D * H;
+      if (reset && reset[(size_t)t * n + e]) memset(ce, 0, sizeof(float) * nt.D * H);
+      pol_forward(nt, obs + ((size_t)t * n + e) * ZB_POL_ACTOR_IN, ce, out.data());
+      float* act = actions + ((size_t)t * n + e) * NJ;
+      for (int j = 0; j < NJ; j++) {
+        float mu[ZB_POL_MAX_MIX], sd[ZB_POL_MAX_MIX], lg[ZB_POL_MAX_MIX];
+        for (int m = 0; m < nm; m++) {
+          mu[m] = out[j * nm + m] + nt.mean_bias[j];
+          const float sp = (zbf_softplus(out[NJ * nm + j * nm + m]) + 0.01f) * 1.0f;
+          sd[m] = sp < 1.0f ? sp : 1.0f;
+          lg[m] = out[2 * NJ * nm + j * nm + m];
+        }
+        if (mode != ZB_POL_EVAL)
+          act[j] = zbf_mix_sample_n(mu, sd, lg, nm, mode == ZB_POL_MODE, seed, ZB_RNG_POLICY, (uint32_t)j,
+                                    (uint32_t)(NJ + j), (uint32_t)(env_offset + e), step0 + (uint32_t)t);
+        if (log_prob) log_prob[((size_t)t * n + e) * NJ + j] = zbf_mix_log_prob_n(mu, sd, lg, nm, act[j]);
+      }
+    }
+  return ZB_OK;
+}
+
+int zb_policy_critic_host(const ZbPolicyShape* s, const float* params, const float* obs, int T, int n, float* carry,
+                          const uint8_t* reset, float* value) {
+  const int rc = pol_host_check("zb_policy_critic_host", ZB_POL_CRITIC, s, params, obs, T, n, carry, 0);
+  if (rc != ZB_OK) return rc == 1 ? ZB_OK : rc;
+  if (!value) return fail(ZB_EARG, "zb_policy_critic_host: null value");
+  constexpr int H = ZB_POL_HIDDEN;
+  const PolNet nt = pol_net(params, ZB_POL_CRITIC, s);
+  for (int t = 0; t < T; t++)
+    for (int e = 0; e < n; e++) {
+      float* ce = carry + (size_t)e * nt.D * H;
+      if (reset && reset[(size_t)t * n + e]) memset(ce, 0, sizeof(float) * nt.D * H);
+      pol_forward(nt, obs + ((size_t)t * n + e) * ZB_POL_CRITIC_IN, ce, value + (size_t)t * n + e);
+    }
+  return ZB_OK;
+}
 
 int zb_command_initial_host(const ZbCommandConfig* cfg, uint64_t seed, const uint32_t* env, const uint32_t* counter,
                             const float* quat, float ctrl_dt, int n, float* out) {

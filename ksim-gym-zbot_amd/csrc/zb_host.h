@@ -12,6 +12,7 @@
 
 #include "zbot.h"
 #include "zbot_command.h"
+#include "zbot_policy.h"
 #include "zbot_ppo.h"
 
 namespace zb {
@@ -90,6 +91,9 @@ int check_adamw_args(const char* what, const void* param, const void* grad, cons
 float inv_total(double total);
 struct AdamCoef { float beta1, omb1, beta2, omb2, bc1, bc2; };
 AdamCoef adam_coefficients(double beta1, double beta2, int step);
+
+/* a ZbPolicyShape (include/zbot_policy.h "Network shape"): ZB_OK, or ZB_EARG with the field named */
+int check_policy_shape(const char* what, int kind, const ZbPolicyShape* shape);
 
 /* zb_minibatch_gather / _host (include/zbot_ppo.h "Minibatches"): the argument check, which also
    fills out[n_items] with each item and the access width it moves in: the widest of 16, 8, 4, 1

@@ -133,7 +133,13 @@ struct PolicyArgs {
   float* save;            /* training forward (zb_policy_*_train): scratch base, else null; carry is then
                              read-only (carry0) */
 };
-hipError_t launch_policy(int kind, const PolicyArgs& a, hipStream_t s);
+/* what a launch is given: PolicyArgs, which the default-shape kernels take as it is, and the handle's shape
+   (include/zbot_policy.h "Network shape"), which only the shape-generic instantiations take */
+struct PolicyArgsG : PolicyArgs {
+  int generic;            /* 1: the shape-generic instantiations, which read depth and nmix below */
+  int depth, nmix;
+};
+hipError_t launch_policy(int kind, const PolicyArgsG& a, hipStream_t s);
 
 /* Training scratch (include/zbot_policy.h): planes of K = T n rows in (t, env) order, offsets in
    fp32 words. Per-layer planes are [layer][K][cols]. */
@@ -153,6 +159,7 @@ struct TrainLayout {
   size_t total;
   int chunks;   /* split-K chunks of the parameter gradient */
   int chunk_rows;
+  size_t dht;   /* train_layout_shaped only: [D][n][H] d loss / d carry handed to step t - 1 */
 };
 __host__ __device__ static inline size_t policy_param_count(int kind) {
   const size_t H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH;
@@ -182,6 +189,44 @@ __host__ __device__ static inline TrainLayout train_layout(int kind, int T, int 
   L.chunk_rows = (int)(((K + c - 1) / c + 15) / 16 * 16);
   L.part = o, o += c * policy_param_count(kind);
   L.total = o;
+  L.dht = 0;
+  return L;
+}
+
+/* The layout of a shaped handle's scratch: D layers, a raw-head row stride of 60 m rounded up to 16
+   (policy_raw_ld), and the plane dht [D][n][H] in which the generic bptt_kernel hands the
+   time-direction gradient of every layer to step t - 1 (the default kernel holds it in registers). */
+__host__ __device__ static inline size_t policy_param_count_shaped(int kind, int depth, int nmix) {
+  const size_t H = ZB_POL_HIDDEN, D = (size_t)depth;
+  const size_t I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN;
+  const size_t O = kind == ZB_POL_ACTOR ? (size_t)3 * ZB_POL_JOINTS * (size_t)nmix : 1;
+  return H * I + H + D * (6 * H * H + 4 * H) + O * H + O + (kind == ZB_POL_ACTOR ? ZB_POL_JOINTS : 0);
+}
+__host__ __device__ static inline int policy_raw_ld(int nmix) { return (3 * ZB_POL_JOINTS * nmix + 15) / 16 * 16; }
+__host__ __device__ static inline TrainLayout train_layout_shaped(int kind, int depth, int nmix, int T, int n) {
+  TrainLayout L;
+  const size_t H = ZB_POL_HIDDEN, D = (size_t)depth, K = (size_t)T * (size_t)n;
+  const size_t act = kind == ZB_POL_ACTOR ? K * (size_t)policy_raw_ld(nmix) : 0;
+  size_t o = 0;
+  L.K = K;
+  L.x0 = o, o += K * H;
+  L.hp = o, o += D * K * H;
+  L.r = o, o += D * K * H;
+  L.z = o, o += D * K * H;
+  L.nn = o, o += D * K * H;
+  L.hn = o, o += D * K * H;
+  L.ho = o, o += D * K * H;
+  L.raw = o, o += act;
+  L.dg = o, o += D * K * ZB_TR_DG_LD;
+  L.dx0 = o, o += K * H;
+  L.draw = o, o += act;
+  L.dht = o, o += D * (size_t)n * H;
+  size_t c = (K + 511) / 512;
+  c = c < 1 ? 1 : (c > ZB_TR_MAX_CHUNKS ? ZB_TR_MAX_CHUNKS : c);
+  L.chunks = (int)c;
+  L.chunk_rows = (int)(((K + c - 1) / c + 15) / 16 * 16);
+  L.part = o, o += c * policy_param_count_shaped(kind, depth, nmix);
+  L.total = o;
   return L;
 }
 
@@ -196,9 +241,13 @@ struct PolicyBwdArgs {
   const float* bias;      /* as PolicyArgs::bias */
   int T, n;
 };
-hipError_t launch_policy_backward(int kind, const PolicyBwdArgs& a, hipStream_t s);
-/* device repack of natural-layout parameters into wpack / wpack_t / bias */
-hipError_t launch_policy_pack(int kind, const float* params, float* wpack, float* wpack_t, float* bias, hipStream_t s);
+struct PolicyBwdArgsG : PolicyBwdArgs {
+  int generic, depth, nmix; /* as PolicyArgsG */
+};
+hipError_t launch_policy_backward(int kind, const PolicyBwdArgsG& a, hipStream_t s);
+/* device repack of natural-layout parameters into wpack / wpack_t / bias (depth layers, nmix mixtures) */
+hipError_t launch_policy_pack(int kind, int depth, int nmix, const float* params, float* wpack, float* wpack_t,
+                              float* bias, hipStream_t s);
 
 hipError_t launch_normalize(const float* gae, float* adv, long long count, const double* mom, double total,
                             float eps, hipStream_t s);

@@ -107,13 +107,35 @@ __device__ __forceinline__ void tile_gemm(const float* xs, const float4* wp, int
 /* SAVE: the training forward (zb_policy_*_train): the same arithmetic, with the carry read
    from carry0 and never written back, and what backward needs stored per (t, env) row of the scratch
    planes (zb_internal.h TrainLayout). Only stores are added, so the bits are those of SAVE = false. */
-template <int KIN, int NOUT, bool ACTOR, bool PERSIST, bool SAVE = false>
-__global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) {
+/* GEN: the shape-generic instantiation (include/zbot_policy.h "Network shape"): depth and mixture count are
+   the runtime values a0.depth <= ZB_POL_MAX_DEPTH and a0.nmix <= ZB_POL_MAX_MIX, NOUT is the actor's largest
+   output count (it sizes the LDS tile) and the live one is 60 nmix. The chains, the epilogue and the head
+   are the code below either way, so at depth 5 and 5 mixtures the bits are those of GEN = false. Its
+   persistent form keeps no carry registers: a thread reads back the 8 (unit, env) values of a layer it
+   wrote at the previous step, from the carry (written at every step, not only the last) or, under SAVE,
+   from the previous row of the saved layer outputs. */
+template <bool GEN>
+struct KArgs { typedef PolicyArgs type; };
+template <>
+struct KArgs<true> { typedef PolicyArgsG type; };
+/* compile-time constants for the default-shape kernels, runtime values for the shape-generic ones */
+__device__ __forceinline__ constexpr int arg_depth(const PolicyArgs&) { return D; }
+__device__ __forceinline__ int arg_depth(const PolicyArgsG& a) { return a.depth; }
+__device__ __forceinline__ constexpr int arg_nmix(const PolicyArgs&) { return NMIX; }
+__device__ __forceinline__ int arg_nmix(const PolicyArgsG& a) { return a.nmix; }
+
+template <int KIN, int NOUT, bool ACTOR, bool PERSIST, bool SAVE = false, bool GEN = false>
+__global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(typename KArgs<GEN>::type a0) {
 #pragma clang fp contract(off)
   constexpr int KPAD = (KIN + 15) / 16 * 16;
   constexpr int GIN = KPAD / 16;
-  constexpr int NTO = (NOUT + 15) / 16;
   constexpr int OUTS = NOUT + 1;
+  const int Dn = arg_depth(a0);                                   /* GRU layers */
+  const int nmix = arg_nmix(a0);                                  /* mixture components */
+  const int nout = GEN && ACTOR ? 3 * NJ * nmix : NOUT;           /* live outputs */
+  const int nto = (nout + 15) / 16;
+  const int outs = nout + 1;                                      /* row stride of the output tile */
+  const int rawld = GEN ? policy_raw_ld(nmix) : ZB_TR_RAW_LD;     /* row stride of the saved raw outputs */
   constexpr int XIN = KPAD * LDU;
   constexpr int OUTW = ACTOR ? M * OUTS : 1;
   constexpr int UW = XIN > OUTW ? XIN : OUTW;
@@ -132,9 +154,10 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
      and once after the last step. Every product is the same k-ordered chain as one launch per step,
      so the results are the same bits. */
   const int TT = PERSIST && a0.T > 1 ? a0.T : 1;
-  float hreg[D][NET][4];
+  constexpr int DR = GEN ? 1 : D;
+  [[maybe_unused]] float hreg[DR][NET][4];
 #pragma unroll
-  for (int l = 0; l < D; ++l)
+  for (int l = 0; l < DR; ++l)
 #pragma unroll
     for (int et = 0; et < NET; ++et)
 #pragma unroll
@@ -151,7 +174,10 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
   [[maybe_unused]] TrainLayout tl;
   [[maybe_unused]] size_t row0 = 0; /* scratch row of this block's env 0 at step t */
   if constexpr (SAVE) {
-    tl = train_layout(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, a0.T, a0.n);
+    if constexpr (GEN)
+      tl = train_layout_shaped(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, Dn, nmix, a0.T, a0.n);
+    else
+      tl = train_layout(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, a0.T, a0.n);
     row0 = (size_t)t * a0.n + e0;
   }
 
@@ -166,7 +192,7 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
       const int ge = e0 + e;
       cr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (ge < a.n && !(a.reset && a.reset[ge]))
-        cr[j] = *reinterpret_cast<const float4*>(a.carry + ((size_t)ge * D + l) * H + 4 * q);
+        cr[j] = *reinterpret_cast<const float4*>(a.carry + ((size_t)ge * Dn + l) * H + 4 * q);
     }
   };
   if (t == 0) load_carry(0); /* layer 0's carry loads overlap the observation tile and input projection */
@@ -241,7 +267,7 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
   const size_t off_gru = (size_t)(H / 16) * GIN * 64;  /* float4 offset of layer 0's W_ih pack */
   constexpr size_t MAT = (size_t)(3 * H / 16) * GH * 64; /* one packed [3H][H] matrix, float4 */
   int cur = 0;
-  for (int l = 0; l < D; ++l) {
+  for (int l = 0; l < Dn; ++l) {
     if (t == 0) {
       /* carry of layer l (prefetched during layer l - 1) -> sh */
 #pragma unroll
@@ -261,15 +287,28 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int e = crow(et, v, lane), ge = e0 + e;
-          float hv = hreg[0][et][v];
+          if constexpr (GEN) {
+            /* what this thread stored for (layer l, env, unit) at step t - 1 */
+            const bool rs = ge >= a.n || (a.reset && a.reset[ge]);
+            float hv = 0.f;
+            if (!rs) {
+              if constexpr (SAVE)
+                hv = a0.save[tl.ho + ((size_t)l * tl.K + (row0 - (size_t)a0.n) + e) * H + unit];
+              else
+                hv = a.carry[((size_t)ge * Dn + l) * H + unit];
+            }
+            sh[unit * LDA + e] = hv;
+          } else {
+            float hv = hreg[0][et][v];
 #pragma unroll
-          for (int k = 1; k < D; ++k) hv = l == k ? hreg[k][et][v] : hv;
-          const bool rs = ge >= a.n || (a.reset && a.reset[ge]);
-          sh[unit * LDA + e] = rs ? 0.f : hv;
+            for (int k = 1; k < D; ++k) hv = l == k ? hreg[k][et][v] : hv;
+            const bool rs = ge >= a.n || (a.reset && a.reset[ge]);
+            sh[unit * LDA + e] = rs ? 0.f : hv;
+          }
         }
     }
     __syncthreads();
-    if (t == 0 && l + 1 < D) load_carry(l + 1);
+    if (t == 0 && l + 1 < Dn) load_carry(l + 1);
 
     const float4* wih = wp4 + off_gru + (size_t)l * 2 * MAT + lane;
     const float4* whh = wih + MAT;
@@ -346,11 +385,13 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
             a0.save[tl.ho + i] = hv;
           }
         } else {
-          if (last && e0 + e < a.n) a.carry[((size_t)(e0 + e) * D + l) * H + unit] = hv;
+          if ((last || GEN) && e0 + e < a.n) a.carry[((size_t)(e0 + e) * Dn + l) * H + unit] = hv;
         }
-        if (TT > 1) {
+        if constexpr (!GEN) {
+          if (TT > 1) {
 #pragma unroll
-          for (int k = 0; k < D; ++k) hreg[k][et][v] = l == k ? hv : hreg[k][et][v];
+            for (int k = 0; k < D; ++k) hreg[k][et][v] = l == k ? hv : hreg[k][et][v];
+          }
         }
       }
     }
@@ -360,53 +401,67 @@ __global__ __launch_bounds__(NTHR) ZB_POL_OCC void policy_kernel(PolicyArgs a0) 
 
   /* 4. heads */
   const float* xs = sx[cur];
-  const float* tail = a.bias + H + (size_t)D * 4 * H; /* output bias [NOUT], then head constants */
+  const float* tail = a.bias + H + (size_t)Dn * 4 * H; /* output bias [nout], then head constants */
   if constexpr (ACTOR) {
     /* output projection (train.py:950) into su[env][c] */
-    const float4* wo = wp4 + off_gru + (size_t)D * 2 * MAT + lane;
-    for (int nt = w; nt < NTO; nt += NWAVE) {
+    const float4* wo = wp4 + off_gru + (size_t)Dn * 2 * MAT + lane;
+    for (int nt = w; nt < nto; nt += NWAVE) {
       f32x4 acc[NET];
       tile_gemm<LDA>(xs, wo + (size_t)nt * GH * 64, GH, lane, acc);
       const int c = nt * 16 + c16;
-      if (c < NOUT) {
+      if (c < nout) {
         const float bc = tail[c];
 #pragma unroll
         for (int et = 0; et < NET; ++et)
 #pragma unroll
           for (int v = 0; v < 4; ++v) {
             const int e = crow(et, v, lane);
-            su[e * OUTS + c] = acc[et][v] + bc;
+            su[e * outs + c] = acc[et][v] + bc;
             if constexpr (SAVE) {
-              if (e0 + e < a.n) a0.save[tl.raw + (row0 + e) * ZB_TR_RAW_LD + c] = acc[et][v] + bc;
+              if (e0 + e < a.n) a0.save[tl.raw + (row0 + e) * rawld + c] = acc[et][v] + bc;
             }
           }
       }
     }
     __syncthreads();
     /* mixture head per (env, joint) (train.py:952-965) */
-    const float* mean_bias = tail + NOUT;
+    const float* mean_bias = tail + nout;
     for (int it = tid; it < M * NJ; it += NTHR) {
       const int e = it / NJ, j = it - e * NJ, ge = e0 + e;
       if (ge >= a.n) continue;
-      const float* o = su + e * OUTS;
-      float mu[NMIX], sd[NMIX], lg[NMIX];
+      const float* o = su + e * outs;
+      constexpr int MM = GEN ? ZB_POL_MAX_MIX : NMIX;
+      float mu[MM], sd[MM], lg[MM];
 #pragma unroll
-      for (int m = 0; m < NMIX; ++m) {
-        mu[m] = o[j * NMIX + m] + mean_bias[j];
-        const float s = (zbf_softplus(o[NJ * NMIX + j * NMIX + m]) + 0.01f) * 1.0f;
+      for (int m = 0; m < MM; ++m) {
+        if constexpr (GEN) {
+          mu[m] = sd[m] = lg[m] = 0.f;
+          if (m >= nmix) continue;
+        }
+        mu[m] = o[j * nmix + m] + mean_bias[j];
+        const float s = (zbf_softplus(o[NJ * nmix + j * nmix + m]) + 0.01f) * 1.0f;
         sd[m] = s < 1.0f ? s : 1.0f;
-        lg[m] = o[2 * NJ * NMIX + j * NMIX + m];
+        lg[m] = o[2 * NJ * nmix + j * nmix + m];
       }
       const size_t ai = (size_t)ge * NJ + j;
       float act;
       if (a.mode == ZB_POL_EVAL) {
         act = a.actions[ai];
       } else {
-        act = zbf_mix_sample(mu, sd, lg, a.mode == ZB_POL_MODE, a.seed, ZB_RNG_POLICY, (uint32_t)j,
-                             (uint32_t)(NJ + j), (uint32_t)(a.env_offset + ge), a.step);
+        if constexpr (GEN)
+          act = zbf_mix_sample_n(mu, sd, lg, nmix, a.mode == ZB_POL_MODE, a.seed, ZB_RNG_POLICY, (uint32_t)j,
+                                 (uint32_t)(NJ + j), (uint32_t)(a.env_offset + ge), a.step);
+        else
+          act = zbf_mix_sample(mu, sd, lg, a.mode == ZB_POL_MODE, a.seed, ZB_RNG_POLICY, (uint32_t)j,
+                               (uint32_t)(NJ + j), (uint32_t)(a.env_offset + ge), a.step);
         a.actions[ai] = act;
       }
-      if (a.log_prob) a.log_prob[ai] = zbf_mix_log_prob(mu, sd, lg, act);
+      if (a.log_prob) {
+        if constexpr (GEN)
+          a.log_prob[ai] = zbf_mix_log_prob_n(mu, sd, lg, nmix, act);
+        else
+          a.log_prob[ai] = zbf_mix_log_prob(mu, sd, lg, act);
+      }
     }
   } else {
     /* value head (train.py:1017): one fmaf chain per env, natural-layout W_out */
@@ -633,8 +688,11 @@ __global__ __launch_bounds__(64 * NWV, 2) void policy_wave_kernel(PolicyArgs a) 
 
 }  // namespace pol
 
-hipError_t launch_policy(int kind, const PolicyArgs& a, hipStream_t s) {
+hipError_t launch_policy(int kind, const PolicyArgsG& ag, hipStream_t s) {
+  const PolicyArgs& a = ag; /* the default-shape kernels take the launch without the shape */
   if (a.n <= 0) return hipSuccess;
+  /* the slot-sized kernels are compiled for the default shape only (zb_policy_set_layout refuses them) */
+  if (ag.generic && a.layout != ZB_POL_LAYOUT_BLOCK) return hipErrorInvalidValue;
   if (a.layout == ZB_POL_LAYOUT_WAVE || a.layout == ZB_POL_LAYOUT_WAVE2 || a.layout == ZB_POL_LAYOUT_WAVE4) {
     const int nw = (a.n + pol::WM - 1) / pol::WM;
     if (a.layout == ZB_POL_LAYOUT_WAVE4) {
@@ -660,6 +718,27 @@ hipError_t launch_policy(int kind, const PolicyArgs& a, hipStream_t s) {
   }
   const int nblk = (a.n + pol::M - 1) / pol::M;
   const bool persist = a.T > 1;
+  if (ag.generic) {
+    /* shaped handles: one instantiation per form, sized for the two maxima */
+    constexpr int GO = 3 * ZB_POL_JOINTS * ZB_POL_MAX_MIX;
+    const dim3 g(nblk), b(pol::NTHR);
+    if (kind == ZB_POL_ACTOR) {
+      if (a.save)
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, GO, true, true, true, true>), g, b, 0, s, ag);
+      else if (persist)
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, GO, true, true, false, true>), g, b, 0, s, ag);
+      else
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, GO, true, false, false, true>), g, b, 0, s, ag);
+    } else {
+      if (a.save)
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_CRITIC_IN, 1, false, true, true, true>), g, b, 0, s, ag);
+      else if (persist)
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_CRITIC_IN, 1, false, true, false, true>), g, b, 0, s, ag);
+      else
+        hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_CRITIC_IN, 1, false, false, false, true>), g, b, 0, s, ag);
+    }
+    return hipGetLastError();
+  }
   if (a.save) {
     if (kind == ZB_POL_ACTOR)
       hipLaunchKernelGGL((pol::policy_kernel<ZB_POL_ACTOR_IN, ZB_POL_ACTOR_OUT, true, true, true>), dim3(nblk),

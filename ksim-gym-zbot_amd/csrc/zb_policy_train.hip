@@ -47,7 +47,6 @@ constexpr int NJ = ZB_POL_JOINTS;
 constexpr int NMIX = ZB_POL_MIX;
 constexpr int G3 = 3 * H / 16;               /* 4-step groups over K = 3H */
 constexpr int RAWP = ZB_TR_RAW_LD;           /* 300 padded to a multiple of 16 */
-constexpr int GO = RAWP / 16;
 constexpr size_t MATT = (size_t)NWAVE * G3 * 64; /* one packed [H][3H] transposed matrix, float4 */
 static_assert(RAWP % 16 == 0 && RAWP >= ZB_POL_ACTOR_OUT, "padded head width");
 static_assert(ZB_TR_DG_LD == 4 * H, "four gradient rows per unit");
@@ -131,25 +130,121 @@ __global__ __launch_bounds__(256) void head_kernel(PolicyBwdArgs a) {
                 a.scratch + tl.draw + row * RAWP);
 }
 
-template <bool ACTOR>
-__global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
+/* The same head backward over nm <= ZB_POL_MAX_MIX components (shaped handles): the operations and their
+   order are mix_head_grad's with nm in place of NMIX, the loops run over the maximum behind a guard so
+   that they unroll and the arrays stay in registers. At nm = 5 the bits are mix_head_grad's. */
+__device__ __forceinline__ void mix_head_grad_n(const float* o, float mb, float g, float act, int j, int nm,
+                                                float* dr) {
+  constexpr int MM = ZB_POL_MAX_MIX;
+  float mu[MM], sd[MM], lg[MM], sraw[MM];
+  bool open[MM];
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    mu[m] = sd[m] = lg[m] = sraw[m] = 0.f;
+    open[m] = false;
+    if (m >= nm) continue;
+    mu[m] = o[j * nm + m] + mb;
+    sraw[m] = o[NJ * nm + j * nm + m];
+    const float s = (zbf_softplus(sraw[m]) + 0.01f) * 1.0f;
+    open[m] = s < 1.0f;
+    sd[m] = open[m] ? s : 1.0f;
+    lg[m] = o[2 * NJ * nm + j * nm + m];
+  }
+  float mx = lg[0];
+#pragma unroll
+  for (int m = 1; m < MM; ++m)
+    if (m < nm) mx = lg[m] > mx ? lg[m] : mx;
+  float pe[MM], Ssum = 0.f;
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    pe[m] = 0.f;
+    if (m >= nm) continue;
+    pe[m] = zbf_exp(lg[m] - mx);
+    Ssum = Ssum + pe[m];
+  }
+  const float logS = zbf_log(Ssum);
+  float vv[MM], zz[MM], Mx = -3.0e38f;
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    vv[m] = zz[m] = 0.f;
+    if (m >= nm) continue;
+    zz[m] = (act - mu[m]) / sd[m];
+    const float lnm = ((-0.5f * zz[m]) * zz[m] - zbf_log(sd[m])) - ZBF_HALF_LOG_2PI;
+    vv[m] = ((lg[m] - mx) - logS) + lnm;
+    Mx = vv[m] > Mx ? vv[m] : Mx;
+  }
+  float we[MM], acc = 0.f;
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    we[m] = 0.f;
+    if (m >= nm) continue;
+    we[m] = zbf_exp(vv[m] - Mx);
+    acc = acc + we[m];
+  }
+#pragma unroll
+  for (int m = 0; m < MM; ++m) {
+    if (m >= nm) continue;
+    const float wm = we[m] / acc;
+    const float dlg = g * (wm - pe[m] / Ssum);
+    const float dmu = g * (wm * (zz[m] / sd[m]));
+    const float dsr = open[m] ? g * (wm * ((zz[m] * zz[m] - 1.0f) / sd[m])) * zbf_sigmoid(sraw[m]) : 0.f;
+    dr[j * nm + m] = dmu;
+    dr[NJ * nm + j * nm + m] = dsr;
+    dr[2 * NJ * nm + j * nm + m] = dlg;
+  }
+}
+
+__global__ __launch_bounds__(256) void head_kernel_n(PolicyBwdArgsG a) {
+#pragma clang fp contract(off)
+  const TrainLayout tl = train_layout_shaped(ZB_POL_ACTOR, a.depth, a.nmix, a.T, a.n);
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= tl.K * NJ) return;
+  const size_t row = i / NJ;
+  const int j = (int)(i - row * NJ);
+  const int rawp = policy_raw_ld(a.nmix);
+  const float* mean_bias = a.bias + H + (size_t)a.depth * 4 * H + 3 * NJ * a.nmix;
+  mix_head_grad_n(a.scratch + tl.raw + row * rawp, mean_bias[j], a.dout[i], a.actions[i], j, a.nmix,
+                  a.scratch + tl.draw + row * rawp);
+}
+
+/* GEN: the shape-generic instantiation (a.depth layers, a.nmix mixtures). It hands the time-direction
+   gradient of every layer to step t - 1 through the scratch plane TrainLayout::dht, each thread reading
+   back the 8 values it wrote, where GEN = false holds them in registers; the arithmetic is the same. */
+template <bool GEN>
+struct BArgs { typedef PolicyBwdArgs type; };
+template <>
+struct BArgs<true> { typedef PolicyBwdArgsG type; };
+__device__ __forceinline__ constexpr int arg_depth(const PolicyBwdArgs&) { return D; }
+__device__ __forceinline__ int arg_depth(const PolicyBwdArgsG& a) { return a.depth; }
+__device__ __forceinline__ constexpr int arg_nmix(const PolicyBwdArgs&) { return NMIX; }
+__device__ __forceinline__ int arg_nmix(const PolicyBwdArgsG& a) { return a.nmix; }
+
+template <bool ACTOR, bool GEN = false>
+__global__ __launch_bounds__(NTHR) void bptt_kernel(typename BArgs<GEN>::type a) {
   constexpr int NOUT = ACTOR ? ZB_POL_ACTOR_OUT : 1;
+  const int Dn = arg_depth(a), nmix = arg_nmix(a);
+  const int nout = GEN && ACTOR ? 3 * NJ * nmix : NOUT;
+  const int rawp = GEN ? policy_raw_ld(nmix) : RAWP;
+  const int go = rawp / 16;
   __shared__ float sg[4 * H * LDA];  /* [da_r | da_z | da_n | da_n r][unit][env]; first the actor's d raw [c][env] */
   __shared__ float sdx[H * LDA];     /* dx from the layer above [unit][env] */
   static_assert(RAWP <= 4 * H, "the head gradient tile fits the gate gradient tile");
+  static_assert(3 * ZB_POL_JOINTS * ZB_POL_MAX_MIX <= 4 * H, "and so does the widest shaped head");
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int c16 = lane & 15, k4 = lane >> 4;
   const int unit = 16 * w + c16;
   const int e0 = blockIdx.x * M;
-  const TrainLayout tl = train_layout(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, a.T, a.n);
+  const TrainLayout tl = GEN ? train_layout_shaped(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, Dn, nmix, a.T, a.n)
+                             : train_layout(ACTOR ? ZB_POL_ACTOR : ZB_POL_CRITIC, a.T, a.n);
   const float4* wt4 = reinterpret_cast<const float4*>(a.wpack_t);
-  const float* tail = a.bias + H + (size_t)D * 4 * H; /* output bias [NOUT], then head constants */
+  const float* tail = a.bias + H + (size_t)Dn * 4 * H; /* output bias [nout], then head constants */
   float* S = a.scratch;
 
-  float dht[D][NET][4]; /* d loss / d carry handed to step t - 1, per layer */
+  constexpr int DR = GEN ? 1 : D;
+  [[maybe_unused]] float dht[DR][NET][4]; /* d loss / d carry handed to step t - 1, per layer */
 #pragma unroll
-  for (int l = 0; l < D; ++l)
+  for (int l = 0; l < DR; ++l)
 #pragma unroll
     for (int et = 0; et < NET; ++et)
 #pragma unroll
@@ -161,21 +256,21 @@ __global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
     if constexpr (ACTOR) {
       /* the step's d raw rows (head_kernel) -> sg [c][env], zero past the 300 outputs and the last env */
 #pragma unroll 1
-      for (int i = tid; i < M * RAWP; i += NTHR) {
-        const int e = i / RAWP, c = i - e * RAWP;
-        sg[c * LDA + e] = (e0 + e < a.n && c < NOUT) ? S[tl.draw + (row0 + e) * RAWP + c] : 0.f;
+      for (int i = tid; i < M * rawp; i += NTHR) {
+        const int e = i / rawp, c = i - e * rawp;
+        sg[c * LDA + e] = (e0 + e < a.n && c < nout) ? S[tl.draw + (row0 + e) * rawp + c] : 0.f;
       }
       __syncthreads();
       /* d h_top = d raw [32][300] W_out [300][128]: this wave's 16 units */
       {
-        const float4* wo = wt4 + (size_t)D * 2 * MATT + (size_t)w * GO * 64 + lane;
+        const float4* wo = wt4 + (size_t)Dn * 2 * MATT + (size_t)w * go * 64 + lane;
         f32x4 acc[NET];
 #pragma unroll
         for (int et = 0; et < NET; ++et) acc[et] = f32x4{0.f, 0.f, 0.f, 0.f};
         float4 b = wo[0];
 #pragma unroll 1
-        for (int g = 0; g < GO; ++g) {
-          const float4 bn = wo[(size_t)(g + 1 < GO ? g + 1 : g) * 64];
+        for (int g = 0; g < go; ++g) {
+          const float4 bn = wo[(size_t)(g + 1 < go ? g + 1 : g) * 64];
           const float* xp = sg + (16 * g + k4) * LDA + c16;
 #pragma unroll
           for (int u = 0; u < 4; ++u)
@@ -189,7 +284,7 @@ __global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
           for (int v = 0; v < 4; ++v) sdx[unit * LDA + crow(et, v, lane)] = acc[et][v];
       }
     } else {
-      const float wu = tail[NOUT + unit]; /* value head W_out [H] */
+      const float wu = tail[nout + unit]; /* value head W_out [H] */
 #pragma unroll
       for (int et = 0; et < NET; ++et)
 #pragma unroll
@@ -203,7 +298,7 @@ __global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
     /* 2. layers D-1 .. 0 */
     /* not unrolled: five copies of the layer body cost the actor 16 to 23 spilled registers */
 #pragma unroll 1
-    for (int l = D - 1; l >= 0; --l) {
+    for (int l = Dn - 1; l >= 0; --l) {
       float dhd[NET][4];
 #pragma unroll
       for (int et = 0; et < NET; ++et)
@@ -211,9 +306,15 @@ __global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
         for (int v = 0; v < 4; ++v) {
           const int e = crow(et, v, lane);
           const bool live = e0 + e < a.n;
-          float dt = dht[0][et][v];
+          float dt;
+          if constexpr (GEN) {
+            /* what this thread stored for (layer l, env, unit) at step t + 1; nothing comes from past the end */
+            dt = (live && t < a.T - 1) ? S[tl.dht + ((size_t)l * a.n + e0 + e) * H + unit] : 0.f;
+          } else {
+            dt = dht[0][et][v];
 #pragma unroll
-          for (int k = 1; k < D; ++k) dt = l == k ? dht[k][et][v] : dt;
+            for (int k = 1; k < D; ++k) dt = l == k ? dht[k][et][v] : dt;
+          }
           const float dhp = sdx[unit * LDA + e] + dt;
           float r = 0.f, z = 0.f, nn = 0.f, hn = 0.f, hp = 0.f;
           const size_t i = ((size_t)l * tl.K + row0 + e) * H + unit;
@@ -276,8 +377,12 @@ __global__ __launch_bounds__(NTHR) void bptt_kernel(PolicyBwdArgs a) {
             S[tl.dx0 + (row0 + e) * H + unit] = ax[et][v];
           const bool cut = ge >= a.n || (a.reset && a.reset[(size_t)t * a.n + ge]);
           const float nd = cut ? 0.f : dhd[et][v] + ah[et][v];
+          if constexpr (GEN) {
+            if (ge < a.n) S[tl.dht + ((size_t)l * a.n + ge) * H + unit] = nd;
+          } else {
 #pragma unroll
-          for (int k = 0; k < D; ++k) dht[k][et][v] = l == k ? nd : dht[k][et][v];
+            for (int k = 0; k < D; ++k) dht[k][et][v] = l == k ? nd : dht[k][et][v];
+          }
         }
       __syncthreads(); /* sg is free for the next layer, sdx holds its upstream */
     }
@@ -303,17 +408,22 @@ struct WJob {
   int tile0, ntn;  /* first tile of this job, tiles along Nc */
 };
 constexpr int MAXJOB = 3 * D + 2;
+constexpr int MAXJOB_GEN = 3 * ZB_POL_MAX_DEPTH + 2; /* the job list of the deepest shaped handle */
 constexpr int WSUB = 512; /* rows of one fp32 chain (a multiple of 16) */
-struct WArgs {
-  WJob job[MAXJOB];
+template <int MJ>
+struct WArgsT {
+  WJob job[MJ];
   int njob;
   long long K;
   int chunk_rows;
   long long pc;    /* parameter count */
   float* part;
 };
+typedef WArgsT<MAXJOB> WArgs;
 
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_kernel(WArgs wa) {
+/* MJ: the capacity of the job list passed by value: MAXJOB at the default shape, MAXJOB_GEN for shaped handles */
+template <int MJ>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void wgrad_kernel(WArgsT<MJ> wa) {
   const int lane = threadIdx.x, c16 = lane & 15, k4 = lane >> 4;
   int ji = 0;
   for (int i = 1; i < wa.njob; ++i) ji = (int)blockIdx.x >= wa.job[i].tile0 ? i : ji;
@@ -439,10 +549,11 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* W, int N, int K,
 
 static size_t pack_words(int N, int K) { return (size_t)((N + 15) / 16) * ((K + 15) / 16) * 256; }
 
-hipError_t launch_policy_pack(int kind, const float* params, float* wpack, float* wpack_t, float* bias,
-                              hipStream_t s) {
-  const int H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH;
-  const int I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN, O = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_OUT : 1;
+hipError_t launch_policy_pack(int kind, int depth, int nmix, const float* params, float* wpack, float* wpack_t,
+                              float* bias, hipStream_t s) {
+  const int H = ZB_POL_HIDDEN, D = depth;
+  const int I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN;
+  const int O = kind == ZB_POL_ACTOR ? 3 * ZB_POL_JOINTS * nmix : 1;
   auto pack = [&](const float* W, int N, int K, int trans, float* out) {
     const size_t words = pack_words(N, K);
     hipLaunchKernelGGL(ptr::pack_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, W, N, K, trans, out);
@@ -482,21 +593,28 @@ hipError_t launch_policy_pack(int kind, const float* params, float* wpack, float
   return hipGetLastError();
 }
 
-hipError_t launch_policy_backward(int kind, const PolicyBwdArgs& a, hipStream_t s) {
-  const int H = ZB_POL_HIDDEN, D = ZB_POL_DEPTH;
-  const int I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN, O = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_OUT : 1;
-  const TrainLayout tl = train_layout(kind, a.T, a.n);
+template <int MJ>
+static hipError_t policy_backward(int kind, const PolicyBwdArgsG& a, hipStream_t s) {
+  constexpr bool GEN = MJ != ptr::MAXJOB;
+  const int H = ZB_POL_HIDDEN, D = GEN ? a.depth : ZB_POL_DEPTH;
+  const int I = kind == ZB_POL_ACTOR ? ZB_POL_ACTOR_IN : ZB_POL_CRITIC_IN;
+  const int O = kind == ZB_POL_ACTOR ? (GEN ? 3 * ZB_POL_JOINTS * a.nmix : ZB_POL_ACTOR_OUT) : 1;
+  const int rawld = GEN ? policy_raw_ld(a.nmix) : ZB_TR_RAW_LD;
+  const TrainLayout tl = GEN ? train_layout_shaped(kind, a.depth, a.nmix, a.T, a.n) : train_layout(kind, a.T, a.n);
   const int nblk = (a.n + ptr::M - 1) / ptr::M;
   if (kind == ZB_POL_ACTOR) {
     const size_t items = tl.K * ZB_POL_JOINTS;
-    hipLaunchKernelGGL(ptr::head_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(ptr::bptt_kernel<true>, dim3(nblk), dim3(ptr::NTHR), 0, s, a);
+    if (GEN)
+      hipLaunchKernelGGL(ptr::head_kernel_n, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(ptr::head_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const PolicyBwdArgs&)a);
+    hipLaunchKernelGGL((ptr::bptt_kernel<true, GEN>), dim3(nblk), dim3(ptr::NTHR), 0, s, (const typename ptr::BArgs<GEN>::type&)a);
   } else
-    hipLaunchKernelGGL(ptr::bptt_kernel<false>, dim3(nblk), dim3(ptr::NTHR), 0, s, a);
+    hipLaunchKernelGGL((ptr::bptt_kernel<false, GEN>), dim3(nblk), dim3(ptr::NTHR), 0, s, (const typename ptr::BArgs<GEN>::type&)a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
 
-  ptr::WArgs wa;
+  ptr::WArgsT<MJ> wa;
   memset(&wa, 0, sizeof wa);
   float* S = a.scratch;
   const size_t KH = tl.K * H;
@@ -524,20 +642,25 @@ hipError_t launch_policy_backward(int kind, const PolicyBwdArgs& a, hipStream_t 
   }
   const float* top = S + tl.ho + (size_t)(D - 1) * KH;
   if (kind == ZB_POL_ACTOR)
-    add(S + tl.draw, ZB_TR_RAW_LD, top, H, O, H, off, off + (long long)O * H);
+    add(S + tl.draw, rawld, top, H, O, H, off, off + (long long)O * H);
   else
     add(a.dout, 1, top, H, 1, H, off, off + H);
   off += (long long)O * H + O;
   wa.njob = nj;
   wa.K = (long long)tl.K;
   wa.chunk_rows = tl.chunk_rows;
-  wa.pc = (long long)policy_param_count(kind);
+  wa.pc = (long long)(GEN ? policy_param_count_shaped(kind, a.depth, a.nmix) : policy_param_count(kind));
   wa.part = S + tl.part;
-  hipLaunchKernelGGL(ptr::wgrad_kernel, dim3(tiles, tl.chunks), dim3(64), 0, s, wa);
+  hipLaunchKernelGGL(ptr::wgrad_kernel<MJ>, dim3(tiles, tl.chunks), dim3(64), 0, s, wa);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(ptr::wreduce_kernel, dim3((unsigned)((wa.pc + 255) / 256)), dim3(256), 0, s,
                      (const float*)wa.part, tl.chunks, wa.pc, off, a.grad);
   return hipGetLastError();
+}
+
+hipError_t launch_policy_backward(int kind, const PolicyBwdArgsG& a, hipStream_t s) {
+  if (a.generic) return policy_backward<ptr::MAXJOB_GEN>(kind, a, s);
+  return policy_backward<ptr::MAXJOB>(kind, a, s);
 }
 
 }  // namespace zb

@@ -316,5 +316,20 @@ class ZbCommandConfig(C.Structure):
     ]
 
 
+class ZbPolicyShape(C.Structure):
+    """include/zbot_policy.h "Network shape": the GRU depth and mixture count of a policy handle."""
+
+    _fields_ = [
+        ("struct_bytes", C.c_int32),
+        ("hidden_size", C.c_int32),
+        ("depth", C.c_int32),
+        ("num_mixtures", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+POL_MAX_DEPTH, POL_MAX_MIX, POL_SHAPE_GENERIC = 8, 8, 1
+
+
 def struct_field_names(cls: type) -> list[str]:
     return [name for name, _ in cls._fields_]

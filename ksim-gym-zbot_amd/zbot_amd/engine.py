@@ -149,6 +149,21 @@ def load_library(path: str | None = None) -> C.CDLL:
     for f in ("zb_policy_set_params", "zb_policy_actor_train", "zb_policy_critic_train", "zb_policy_actor_backward",
               "zb_policy_critic_backward"):
         getattr(L, f).restype = C.c_int
+    # shaped handles and the forward host twins (include/zbot_policy.h "Network shape")
+    shp = C.POINTER(cs.ZbPolicyShape)
+    L.zb_policy_default_shape.argtypes = [shp]
+    L.zb_policy_default_shape.restype = None
+    L.zb_policy_param_count_shaped.argtypes = [C.c_int, shp]
+    L.zb_policy_param_count_shaped.restype = C.c_size_t
+    L.zb_policy_create_shaped.argtypes = [C.c_int, shp, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.zb_policy_get_shape.argtypes = [vp, shp]
+    L.zb_policy_train_scratch_words_shaped.argtypes = [C.c_int, shp, C.c_int, C.c_int]
+    L.zb_policy_train_scratch_words_shaped.restype = C.c_size_t
+    L.zb_policy_actor_host.argtypes = [shp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_uint64, C.c_int, C.c_uint32,
+                                       vp, vp]
+    L.zb_policy_critic_host.argtypes = [shp, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    for f in ("zb_policy_create_shaped", "zb_policy_get_shape", "zb_policy_actor_host", "zb_policy_critic_host"):
+        getattr(L, f).restype = C.c_int
     if L.zb_abi_version() != ABI_VERSION:
         raise ZbError(f"{lp}: ABI version {L.zb_abi_version()}, this binding speaks {ABI_VERSION}: rebuild it")
     if L.zb_model_struct_bytes() != C.sizeof(cs.ZbModel):

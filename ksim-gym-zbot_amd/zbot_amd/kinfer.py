@@ -31,7 +31,7 @@ import warnings
 import numpy as np
 import torch
 
-from .policy import ACTOR, param_count
+from .policy import ACTOR, PolicyShape, param_count
 
 HIDDEN, DEPTH, MIX, JOINTS, ACTOR_IN, ACTOR_OUT = 128, 5, 5, 20, 50, 300
 NUM_COMMANDS = 6  # vx, vy, heading, base height, rx, ry (convert.py:43)
@@ -41,11 +41,20 @@ STEP_OUTPUTS = ["action", "carry_out"]
 INIT_OUTPUTS = ["carry"]
 
 
-def _split_actor(params: np.ndarray) -> dict[str, torch.Tensor]:
+def _shape(shape: PolicyShape | None) -> PolicyShape:
+    shape = PolicyShape() if shape is None else shape
+    if shape.hidden_size != HIDDEN:
+        raise ValueError(f"hidden_size {shape.hidden_size}: only {HIDDEN} is built")
+    return shape
+
+
+def _split_actor(params: np.ndarray, shape: PolicyShape | None = None) -> dict[str, torch.Tensor]:
+    shape = _shape(shape)
     p = np.ascontiguousarray(params, dtype=np.float32).ravel()
-    if p.size != param_count(ACTOR):
-        raise ValueError(f"actor parameters: expected {param_count(ACTOR)} floats, got {p.size}")
+    if p.size != param_count(ACTOR, shape):
+        raise ValueError(f"actor parameters: expected {param_count(ACTOR, shape)} floats, got {p.size}")
     H, off, out = HIDDEN, 0, {}
+    n_out = 3 * JOINTS * shape.num_mixtures
 
     def take(name, *shape):
         nonlocal off
@@ -55,13 +64,13 @@ def _split_actor(params: np.ndarray) -> dict[str, torch.Tensor]:
 
     take("w_in", H, ACTOR_IN)
     take("b_in", H)
-    for layer in range(DEPTH):
+    for layer in range(shape.depth):
         take(f"w_ih{layer}", 3 * H, H)
         take(f"w_hh{layer}", 3 * H, H)
         take(f"b{layer}", 3 * H)
         take(f"bn{layer}", H)
-    take("w_out", ACTOR_OUT, H)
-    take("b_out", ACTOR_OUT)
+    take("w_out", n_out, H)
+    take("b_out", n_out)
     take("mean_bias", JOINTS)
     assert off == p.size
     return out
@@ -97,9 +106,10 @@ def yaw_quat(yaw: torch.Tensor) -> torch.Tensor:
 class ActorStep(torch.nn.Module):
     """convert.py:69-97 step_fn for one robot: (action = dist.mode(), carry')."""
 
-    def __init__(self, params: np.ndarray):
+    def __init__(self, params: np.ndarray, shape: PolicyShape | None = None):
         super().__init__()
-        for k, v in _split_actor(params).items():
+        self.depth, self.mix = _shape(shape).depth, _shape(shape).num_mixtures
+        for k, v in _split_actor(params, shape).items():
             self.register_buffer(k, v)
 
     def observation(self, joint_angles, joint_angular_velocities, quaternion, initial_heading, command):
@@ -116,10 +126,10 @@ class ActorStep(torch.nn.Module):
 
     def act(self, obs, carry):
         """Actor.forward + dist.mode() on a 50-float observation (train.py:885-967)."""
-        H = HIDDEN
+        H, MIX = HIDDEN, self.mix
         x = torch.matmul(self.w_in, obs) + self.b_in
         hs = []
-        for layer in range(DEPTH):  # equinox GRUCell stack (train.py:885-967)
+        for layer in range(self.depth):  # equinox GRUCell stack (train.py:885-967)
             h = carry[layer]
             gi = torch.matmul(getattr(self, f"w_ih{layer}"), x) + getattr(self, f"b{layer}")
             gh = torch.matmul(getattr(self, f"w_hh{layer}"), h)
@@ -140,8 +150,12 @@ class ActorStep(torch.nn.Module):
 class ActorInit(torch.nn.Module):
     """convert.py:63-67 init_fn: the zero carry [depth, hidden]."""
 
+    def __init__(self, depth: int = DEPTH):
+        super().__init__()
+        self.depth = depth
+
     def forward(self):
-        return torch.zeros(DEPTH, HIDDEN)
+        return torch.zeros(self.depth, HIDDEN)
 
 
 @contextlib.contextmanager
@@ -183,23 +197,24 @@ def _export(module: torch.nn.Module, args: tuple, input_names, output_names) -> 
     return f.getvalue()
 
 
-def step_example_inputs() -> tuple:
+def step_example_inputs(depth: int = DEPTH) -> tuple:
     return (torch.zeros(JOINTS), torch.zeros(JOINTS), torch.tensor([1.0, 0.0, 0.0, 0.0]), torch.zeros(1),
-            torch.zeros(NUM_COMMANDS), torch.zeros(DEPTH, HIDDEN))
+            torch.zeros(NUM_COMMANDS), torch.zeros(depth, HIDDEN))
 
 
-def export_onnx(params: np.ndarray) -> tuple[bytes, bytes]:
-    """(init_fn.onnx, step_fn.onnx) ModelProto bytes for the actor parameters."""
-    init = _export(ActorInit(), (), [], INIT_OUTPUTS)
-    step = _export(ActorStep(params).eval(), step_example_inputs(), STEP_INPUTS, STEP_OUTPUTS)
+def export_onnx(params: np.ndarray, shape: PolicyShape | None = None) -> tuple[bytes, bytes]:
+    """(init_fn.onnx, step_fn.onnx) ModelProto bytes for the actor parameters of a `shape` network."""
+    depth = _shape(shape).depth
+    init = _export(ActorInit(depth), (), [], INIT_OUTPUTS)
+    step = _export(ActorStep(params, shape).eval(), step_example_inputs(depth), STEP_INPUTS, STEP_OUTPUTS)
     return init, step
 
 
-def metadata(joint_names: list[str], num_commands: int = NUM_COMMANDS) -> dict:
+def metadata(joint_names: list[str], num_commands: int = NUM_COMMANDS, depth: int = DEPTH) -> dict:
     """PyModelMetadata(joint_names, num_commands, carry_size) (convert.py:99-103)."""
     if len(joint_names) != JOINTS:
         raise ValueError(f"expected {JOINTS} joint names (the hinges without the root, convert.py:60)")
-    return {"joint_names": list(joint_names), "num_commands": int(num_commands), "carry_size": [DEPTH, HIDDEN]}
+    return {"joint_names": list(joint_names), "num_commands": int(num_commands), "carry_size": [int(depth), HIDDEN]}
 
 
 def pack(init_onnx: bytes, step_onnx: bytes, meta: dict) -> bytes:
@@ -222,14 +237,16 @@ def unpack(blob: bytes) -> tuple[bytes, bytes, dict]:
     return files["init_fn.onnx"], files["step_fn.onnx"], json.loads(files["metadata.json"])
 
 
-def export_kinfer(params: np.ndarray, path: str | None = None, joint_names: list[str] | None = None) -> bytes:
-    """convert.py:main for actor parameters in the natural layout (GruPolicy / zb_policy_create)."""
+def export_kinfer(params: np.ndarray, path: str | None = None, joint_names: list[str] | None = None,
+                  shape: PolicyShape | None = None) -> bytes:
+    """convert.py:main for actor parameters in the natural layout (GruPolicy / zb_policy_create), of the
+    network `shape` (default: depth 5, 5 mixtures; the carry and its metadata entry are [depth, 128])."""
     if joint_names is None:
         from .model import JOINT_BIASES
 
         joint_names = [n for n, _, _ in JOINT_BIASES]
-    init, step = export_onnx(params)
-    blob = pack(init, step, metadata(joint_names))
+    init, step = export_onnx(params, shape)
+    blob = pack(init, step, metadata(joint_names, depth=_shape(shape).depth))
     if path is not None:
         with open(path, "wb") as f:
             f.write(blob)

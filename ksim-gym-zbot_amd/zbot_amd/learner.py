@@ -164,6 +164,7 @@ class _ShuffledMinibatches:
         src["adv"], src["vt"] = ppo_inputs.advantages_t, ppo_inputs.value_targets_t
         dev = src["acts"].device
         key = (T, count, dev) + tuple((tuple(x.shape[2:]), x.dtype) for x in src.values())
+        key += (tuple(actor_carry0.shape[1:]), tuple(critic_carry0.shape[1:]))  # [depth, 128] of each network
         b = self._buf.get(key)
         if b is None:
             b = {k: torch.empty((T, count) + tuple(x.shape[2:]), dtype=x.dtype, device=dev) for k, x in src.items()}
@@ -208,7 +209,7 @@ class PpoLearner:
 
         rollout: PolicyRollout.run(T, record_critic=True, critic=...)'s dict (obs_actor, actions,
         log_prob, obs_critic, value). ppo_inputs: zbot_amd.ppo.compute_ppo_inputs' result
-        (advantages_t, value_targets_t). actor_carry0 / critic_carry0 [n, 5, 128]: the carries as
+        (advantages_t, value_targets_t). actor_carry0 / critic_carry0 [n, depth, 128]: the carries as
         they were before the run. reset [T, n]: the rows the run reset its carries with (row 0:
         the previous run's last done flags or None -> zeros; row t: done[t - 1]).
         Minibatches are contiguous env slices of `batch_size` in env order, or with a shuffle_seed

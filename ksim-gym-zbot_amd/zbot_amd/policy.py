@@ -14,6 +14,11 @@ autograd wrapper over both) is zbot_amd.learner.
     values = critic.critic(obs_critic_t, critic.initial_carry(n), reset=resets_t)  # [T, n]
     (obs_critic_t[t] is the observation of the state acted in at step t; PolicyRollout records it)
 
+The network shape (train.py's `depth` and `num_mixtures`, train.py:1065-1076) is a property of the
+handle: `GruPolicy(ACTOR, init_params(ACTOR, 0, shape), shape=PolicyShape(depth=2, num_mixtures=3))`;
+carries are then [n, depth, 128]. `actor_host` / `critic_host` are the CPU bit references at every
+shape.
+
 `PolicyRollout` is ksim's rollout loop with the actor in it: per control step
 one actor launch then one zb_step launch, rows written straight into [T, n]
 buffers on the GPU.
@@ -23,9 +28,11 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
+from . import cstructs as cs
 from .constants import JOINT_BIASES
 from .engine import ZbError, _check, load_library
 
@@ -39,28 +46,58 @@ FLOP_ACTOR = 2 * (ACTOR_IN * HIDDEN + DEPTH * 6 * HIDDEN * HIDDEN + HIDDEN * ACT
 FLOP_CRITIC = 2 * (CRITIC_IN * HIDDEN + DEPTH * 6 * HIDDEN * HIDDEN + HIDDEN)
 
 
-def _dims(kind: int) -> tuple[int, int]:
+MAX_DEPTH, MAX_MIXTURES = cs.POL_MAX_DEPTH, cs.POL_MAX_MIX  # include/zbot_policy.h ZB_POL_MAX_*
+
+
+@dataclasses.dataclass(frozen=True)
+class PolicyShape:
+    """train.py's model fields (hidden_size, depth, num_mixtures; train.py:1065-1076) as a property of a
+    policy handle (include/zbot_policy.h "Network shape"). depth 1..8, num_mixtures 1..8 (read for the
+    actor), hidden_size 128 only; anything else is refused by the library with the field named."""
+
+    depth: int = DEPTH
+    num_mixtures: int = MIXTURES
+    hidden_size: int = HIDDEN
+
+    def cstruct(self, generic: bool = False) -> cs.ZbPolicyShape:
+        return cs.ZbPolicyShape(C.sizeof(cs.ZbPolicyShape), int(self.hidden_size), int(self.depth),
+                                int(self.num_mixtures), cs.POL_SHAPE_GENERIC if generic else 0)
+
+
+def _shape(shape) -> PolicyShape:
+    return PolicyShape() if shape is None else shape
+
+
+def _dims(kind: int, shape: PolicyShape | None = None) -> tuple[int, int]:
     if kind == ACTOR:
-        return ACTOR_IN, ACTOR_OUT
+        return ACTOR_IN, 3 * JOINTS * _shape(shape).num_mixtures
     if kind == CRITIC:
         return CRITIC_IN, 1
     raise ZbError(f"unknown policy kind {kind}")
 
 
-def param_count(kind: int) -> int:
-    I, O = _dims(kind)
-    H, D = HIDDEN, DEPTH
+def param_count(kind: int, shape: PolicyShape | None = None) -> int:
+    I, O = _dims(kind, shape)
+    H, D = _shape(shape).hidden_size, _shape(shape).depth
     return H * I + H + D * (6 * H * H + 4 * H) + O * H + O + (JOINTS if kind == ACTOR else 0)
 
 
-def init_params(kind: int, seed: int = 0) -> np.ndarray:
+def flop_per_step(kind: int, shape: PolicyShape | None = None) -> int:
+    """Matrix-core FLOP per env per step (FMA = 2) of a (kind, shape) network; FLOP_ACTOR / FLOP_CRITIC at
+    the default shape."""
+    I, O = _dims(kind, shape)
+    H, D = _shape(shape).hidden_size, _shape(shape).depth
+    return 2 * (I * H + D * 6 * H * H + H * O)
+
+
+def init_params(kind: int, seed: int = 0, shape: PolicyShape | None = None) -> np.ndarray:
     """Parameters in the natural (equinox) layout of include/zbot_policy.h.
 
     Initialised like equinox [U]: Linear weight and bias ~ U(-1/sqrt(in), 1/sqrt(in)),
     GRUCell weights and biases ~ U(-1/sqrt(hidden), 1/sqrt(hidden)). The actor's trailing
     20 floats are the JOINT_BIASES mean offsets (train.py:61-82, 960)."""
-    I, O = _dims(kind)
-    H, D = HIDDEN, DEPTH
+    I, O = _dims(kind, shape)
+    H, D = _shape(shape).hidden_size, _shape(shape).depth
     rng = np.random.default_rng(seed)
 
     def u(lim, *shape):
@@ -74,14 +111,67 @@ def init_params(kind: int, seed: int = 0) -> np.ndarray:
     if kind == ACTOR:
         parts.append(np.array([b for _, b, _ in JOINT_BIASES]))
     out = np.concatenate([np.asarray(p, dtype=np.float32).ravel() for p in parts])
-    assert out.size == param_count(kind)
+    assert out.size == param_count(kind, shape)
     return out
+
+
+def _host_args(kind, params, obs, carry, reset, shape):
+    """Checked, contiguous numpy arguments of the host twins."""
+    sh = _shape(shape)
+    I, _ = _dims(kind, sh)
+    p = np.ascontiguousarray(np.asarray(params, dtype=np.float32).ravel())
+    if p.size != param_count(kind, sh):
+        raise ZbError(f"{p.size} parameters, expected {param_count(kind, sh)}")
+    o = np.ascontiguousarray(obs, dtype=np.float32)
+    if o.ndim != 3 or o.shape[2] != I:
+        raise ZbError(f"observations must be [T, n, {I}], got {list(o.shape)}")
+    T, n, _ = o.shape
+    c = np.array(carry, dtype=np.float32, order="C")  # a copy: the twin updates it in place
+    if c.shape != (n, sh.depth, sh.hidden_size):
+        raise ZbError(f"carry must be [{n}, {sh.depth}, {sh.hidden_size}], got {list(c.shape)}")
+    r = None if reset is None else np.ascontiguousarray(np.asarray(reset).reshape(T, n), dtype=np.uint8)
+    return sh.cstruct(), p, o, T, n, c, r
+
+
+def _np_ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def actor_host(params, obs, carry, reset=None, mode: int = SAMPLE, seed: int = 0, env_offset: int = 0, step0: int = 0,
+               actions=None, log_prob: bool = False, shape: PolicyShape | None = None):
+    """zb_policy_actor_host: the CPU bit reference of GruPolicy.actor at every shape. obs [T, n, 50],
+    carry [n, depth, 128] (not modified) -> (actions [T, n, 20], log_prob [T, n, 20] or None, new carry)."""
+    st, p, o, T, n, c, r = _host_args(ACTOR, params, obs, carry, reset, shape)
+    if mode == EVAL:
+        if actions is None:
+            raise ZbError("EVAL needs the actions")
+        a = np.array(actions, dtype=np.float32, order="C").reshape(T, n, JOINTS)
+    else:
+        a = np.zeros((T, n, JOINTS), np.float32)
+    lp = np.zeros((T, n, JOINTS), np.float32) if log_prob else None
+    _check(load_library().zb_policy_actor_host(C.byref(st), _np_ptr(p), _np_ptr(o), T, n, _np_ptr(c), _np_ptr(r),
+                                               int(mode), C.c_uint64(seed), int(env_offset), C.c_uint32(step0),
+                                               _np_ptr(a), _np_ptr(lp)))
+    return a, lp, c
+
+
+def critic_host(params, obs, carry, reset=None, shape: PolicyShape | None = None):
+    """zb_policy_critic_host: the CPU bit reference of GruPolicy.critic. obs [T, n, 484] -> (value [T, n],
+    new carry)."""
+    st, p, o, T, n, c, r = _host_args(CRITIC, params, obs, carry, reset, shape)
+    v = np.zeros((T, n), np.float32)
+    _check(load_library().zb_policy_critic_host(C.byref(st), _np_ptr(p), _np_ptr(o), T, n, _np_ptr(c), _np_ptr(r),
+                                                _np_ptr(v)))
+    return v, c
 
 
 class GruPolicy:
     """One actor or critic network on one GPU (a zb_policy handle)."""
 
-    def __init__(self, kind: int, params=None, device: int = 0, seed: int = 0, layout: int | None = None):
+    def __init__(self, kind: int, params=None, device: int = 0, seed: int = 0, layout: int | None = None,
+                 shape: PolicyShape | None = None, generic: bool = False):
+        """shape: the network's PolicyShape (default: depth 5, 5 mixtures). generic: run the shape-generic
+        kernels even at the default shape (bit-identical to the default ones; include/zbot_policy.h)."""
         import torch  # noqa: PLC0415
 
         if not torch.cuda.is_available():
@@ -89,17 +179,27 @@ class GruPolicy:
         self.torch = torch
         self.L = load_library()
         self.kind = kind
-        self.I, self.O = _dims(kind)
+        self.shape = _shape(shape)
+        self.generic = bool(generic)
+        st = self.shape.cstruct(generic)
+        if self.L.zb_policy_param_count_shaped(kind, C.byref(st)) == 0:  # the library names the bad field
+            raise ZbError(f"policy shape refused: {self.L.zb_last_error().decode()}")
+        self.I, self.O = _dims(kind, self.shape)
+        self.n_params = param_count(kind, self.shape)
         self.device = torch.device("cuda", device)
-        p = init_params(kind, seed) if params is None else np.asarray(params, dtype=np.float32).ravel()
+        p = init_params(kind, seed, self.shape) if params is None else np.asarray(params, dtype=np.float32).ravel()
         p = np.ascontiguousarray(p)
-        if p.size != param_count(kind):
-            raise ZbError(f"{p.size} parameters, expected {param_count(kind)}")
+        if p.size != self.n_params:
+            raise ZbError(f"{p.size} parameters, expected {self.n_params}")
         self.params = p
         self._params_dev = None  # device copy of the natural-layout parameters (params_tensor)
         h = C.c_void_p()
-        _check(self.L.zb_policy_create(kind, p.ctypes.data_as(C.POINTER(C.c_float)), p.size, device, C.byref(h)))
+        _check(self.L.zb_policy_create_shaped(kind, C.byref(st), p.ctypes.data_as(C.POINTER(C.c_float)), p.size,
+                                              device, C.byref(h)))
         self.h = h
+        # the handle's own record: flags says which kernels it runs, and so sizes its training scratch
+        self._cshape = cs.ZbPolicyShape()
+        _check(self.L.zb_policy_get_shape(self.h, C.byref(self._cshape)))
         if layout is not None:
             self.set_layout(layout)
 
@@ -119,8 +219,8 @@ class GruPolicy:
         launch of this handle, PolicyRollout's included, runs the new weights."""
         torch = self.torch
         p = self._dev(params.detach().reshape(-1), torch.float32)
-        if p.numel() != param_count(self.kind):
-            raise ZbError(f"{p.numel()} parameters, expected {param_count(self.kind)}")
+        if p.numel() != self.n_params:
+            raise ZbError(f"{p.numel()} parameters, expected {self.n_params}")
         _check(self.L.zb_policy_set_params(self.h, p.data_ptr(), p.numel(), self._stream()))
         self._params_dev = p.clone()
         self.params = None  # the host copy is stale: params_tensor() is the record
@@ -133,7 +233,7 @@ class GruPolicy:
 
     def train_scratch_words(self, T: int, n: int) -> int:
         """fp32 words of scratch a (T, n) training forward writes and its backward reads."""
-        return int(self.L.zb_policy_train_scratch_words(self.kind, int(T), int(n)))
+        return int(self.L.zb_policy_train_scratch_words_shaped(self.kind, C.byref(self._cshape), int(T), int(n)))
 
     def _train_args(self, obs, carry0, reset, scratch):
         torch = self.torch
@@ -151,7 +251,7 @@ class GruPolicy:
 
     def actor_train(self, obs, actions, carry0, reset=None, scratch=None):
         """Training forward of the actor (zb_policy_actor_train): obs [T, n, 50], actions [T, n, 20],
-        carry0 [n, 5, 128] read-only -> (log_prob [T, n, 20] with the bits of actor(mode=EVAL), scratch).
+        carry0 [n, depth, 128] read-only -> (log_prob [T, n, 20] with the bits of actor(mode=EVAL), scratch).
         `scratch` holds the saved activations for actor_backward."""
         if self.kind != ACTOR:
             raise ZbError("actor_train() on a critic handle")
@@ -183,7 +283,7 @@ class GruPolicy:
         o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
         a = self._dev(actions.reshape(T, n, JOINTS), torch.float32)
         d = self._dev(d_log_prob.reshape(T, n, JOINTS), torch.float32)
-        g = self._out(grad, (param_count(self.kind),), torch.float32)
+        g = self._out(grad, (self.n_params,), torch.float32)
         _check(self.L.zb_policy_actor_backward(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
                                                None if r is None else r.data_ptr(), a.data_ptr(), d.data_ptr(),
                                                scratch.data_ptr(), scratch.numel(), g.data_ptr(), self._stream()))
@@ -196,7 +296,7 @@ class GruPolicy:
         torch = self.torch
         o, T, n, r, scratch = self._train_args(obs, carry0, reset, scratch)
         d = self._dev(d_value.reshape(T, n), torch.float32)
-        g = self._out(grad, (param_count(self.kind),), torch.float32)
+        g = self._out(grad, (self.n_params,), torch.float32)
         _check(self.L.zb_policy_critic_backward(self.h, o.data_ptr(), T, n, carry0.data_ptr(),
                                                 None if r is None else r.data_ptr(), d.data_ptr(), scratch.data_ptr(),
                                                 scratch.numel(), g.data_ptr(), self._stream()))
@@ -213,7 +313,7 @@ class GruPolicy:
 
     def initial_carry(self, n: int):
         """get_initial_model_carry (train.py:1731-1735): zeros [n, depth, hidden] per env."""
-        return self.torch.zeros(n, DEPTH, HIDDEN, dtype=self.torch.float32, device=self.device)
+        return self.torch.zeros(n, self.shape.depth, HIDDEN, dtype=self.torch.float32, device=self.device)
 
     def _stream(self) -> int:
         return self.torch.cuda.current_stream(self.device).cuda_stream
@@ -224,9 +324,10 @@ class GruPolicy:
         return t
 
     def _check_carry(self, carry, n):
-        if (tuple(carry.shape) != (n, DEPTH, HIDDEN) or carry.dtype != self.torch.float32
+        D = self.shape.depth
+        if (tuple(carry.shape) != (n, D, HIDDEN) or carry.dtype != self.torch.float32
                 or carry.device != self.device or not carry.is_contiguous()):
-            raise ZbError(f"carry must be a contiguous float32 [{n}, {DEPTH}, {HIDDEN}] tensor on {self.device}")
+            raise ZbError(f"carry must be a contiguous float32 [{n}, {D}, {HIDDEN}] tensor on {self.device}")
 
     def _out(self, t, shape, dtype):
         if t is None:
@@ -238,7 +339,7 @@ class GruPolicy:
 
     def actor(self, obs, carry, reset=None, mode: int = SAMPLE, seed: int = 0, env_offset: int = 0, step: int = 0,
               actions=None, log_prob=False):
-        """obs [n, 50] or [T, n, 50]; carry [n, 5, 128] updated in place; reset [n] / [T, n] uint8
+        """obs [n, 50] or [T, n, 50]; carry [n, depth, 128] updated in place; reset [n] / [T, n] uint8
         (the engine's done flags: carry zeroed before that step). mode SAMPLE / MODE write `actions`,
         EVAL reads them. log_prob: False, True or an output tensor (per joint, [..., 20]).
         Returns (actions, log_prob or None) shaped like obs."""
@@ -270,7 +371,7 @@ class GruPolicy:
         return a, lp
 
     def critic(self, obs, carry, reset=None, value=None):
-        """obs [n, 484] or [T, n, 484]; carry [n, 5, 128] updated in place -> value [n] / [T, n]."""
+        """obs [n, 484] or [T, n, 484]; carry [n, depth, 128] updated in place -> value [n] / [T, n]."""
         torch = self.torch
         if self.kind != CRITIC:
             raise ZbError("critic() on an actor handle")
@@ -332,7 +433,7 @@ class PolicyRollout:
         time limit without a failure (ksim's successes_t for compute_ppo_inputs).
 
         With `critic` (and record_critic), the critic runs inside the loop: V(s_t) right after
-        step t's launch, in the same group chain, with `critic_carry` ([n, 5, 128], updated in
+        step t's launch, in the same group chain, with `critic_carry` ([n, depth, 128], updated in
         place) reset where the previous step ended an episode (none at t = 0), then the bootstrap
         V(s_T) (reset where step T-1 ended one). out["value"] [T, n] and out["value_next"] [n] are
         bit-identical to critic.critic(out["obs_critic"], carry, reset=[0, done[:-1]]) followed by

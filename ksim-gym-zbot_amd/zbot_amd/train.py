@@ -34,6 +34,7 @@ One step(), in order:
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 
 from . import cstructs as cs
 from . import ppo
@@ -41,7 +42,7 @@ from .curriculum import CurriculumState, EpisodeLengthCurriculum, rollout_episod
 from .engine import ZbError
 from .metrics import command_term_means
 from .learner import DEFAULT_BATCH_SIZE, DEFAULT_NUM_PASSES, HipPpoLearner
-from .policy import ACTOR, GruPolicy, PolicyRollout
+from .policy import ACTOR, GruPolicy, PolicyRollout, PolicyShape
 
 DEFAULT_ROLLOUT_STEPS = 200  # rollout_length_seconds 4.0 / ctrl_dt 0.02 (train.py:1775, 1783)
 
@@ -171,6 +172,7 @@ class Trainer:
                          step_count=int(ro.step_count)),
             critic_carry=self.critic_carry.clone(),
             params=dict(actor=self.actor.params_tensor(), critic=self.critic.params_tensor()),
+            shapes=dict(actor=dataclasses.asdict(self.actor.shape), critic=dataclasses.asdict(self.critic.shape)),
             learner=None if self.learner.state is None else self.learner.state_dict(),
             curriculum=dict(level=float(self.cur_state.level), steps=int(self.cur_state.steps)),
             iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle, world=self.world, rank=self.rank,
@@ -189,6 +191,15 @@ class Trainer:
         if int(sd.get("world", 1)) != self.world or int(sd.get("rank", 0)) != self.rank:
             raise ZbError(f"the state is rank {sd.get('rank', 0)}'s of {sd.get('world', 1)}; this Trainer is rank "
                           f"{self.rank} of {self.world}")
+        # the networks' shapes (a state from before shapes existed is of the default one); the critic reads no mixtures
+        default = dataclasses.asdict(PolicyShape())
+        for net, h in (("actor", self.actor), ("critic", self.critic)):
+            want = dict(sd.get("shapes", {}).get(net, default))
+            have = dataclasses.asdict(h.shape)
+            if net == "critic":
+                want.pop("num_mixtures", None), have.pop("num_mixtures", None)
+            if want != have:
+                raise ZbError(f"the state's {net} has the shape {want}; this Trainer's {net} handle has {have}")
         cc = sd.get("command_config")
         if cc is not None and len(cc) != ctypes.sizeof(cs.ZbCommandConfig):
             raise ZbError(f"the state's command config has {len(cc)} bytes, ZbCommandConfig {ctypes.sizeof(cs.ZbCommandConfig)}")
