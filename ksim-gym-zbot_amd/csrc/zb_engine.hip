@@ -273,6 +273,34 @@ __device__ __forceinline__ void dpp_hi4_half(float u[4], const float h[4]) {
       : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3])
       : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
 }
+/* dpp_hi8_mirror for a stage whose slots 4..7 have no hi half (colsum16_pre: 12 columns in 16 slots):
+   the four adds of slots 0..3 only. Both pads stay: the sources may have just been written, and the
+   caller's next stage reads u[3], the last one written here, through DPP in its first instruction at
+   the earliest. */
+__device__ __forceinline__ void dpp_hi4_mirror(float u[4], const float h[4]) {
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %4, %4 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %1, %5, %5 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %2, %6, %6 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "v_add_f32_dpp %3, %7, %7 row_mirror row_mask:0xf bank_mask:0xc\n\t"
+      "s_nop 1"
+      : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3])
+      : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
+}
+/* dpp_hi4_half without the pad behind the adds, for a caller whose next stage is in the select form:
+   that stage reads u[] as the operands of v_cndmask, not through DPP, and what it does read through
+   DPP is the select's result, a VALU write that the compiler's hazard recognizer sees. No DPP read of
+   u[] follows, so the DPP-after-VALU hazard has nothing to wait for. The pad in front stays (the
+   sources may have just been written). */
+__device__ __forceinline__ void dpp_hi4_half_sel(float u[4], const float h[4]) {
+  asm("s_nop 1\n\t"
+      "v_add_f32_dpp %0, %4, %4 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %1, %5, %5 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %2, %6, %6 row_half_mirror row_mask:0xf bank_mask:0xa\n\t"
+      "v_add_f32_dpp %3, %7, %7 row_half_mirror row_mask:0xf bank_mask:0xa"
+      : "+v"(u[0]), "+v"(u[1]), "+v"(u[2]), "+v"(u[3])
+      : "v"(h[0]), "v"(h[1]), "v"(h[2]), "v"(h[3]));
+}
 /* 21 team sums (the root Schur complement), written to out[0..20] in LDS: a
  * transposing butterfly instead of 21 all-lane reductions. Rows 0/1 of the team
  * first exchange halves with v_permlane16_swap (value i stays in row 0, value
@@ -3062,7 +3090,13 @@ __device__ __forceinline__ float rows_cost(const Ctx& c, const Rows& r, float jc
    xor 2, quad xor 1). At each stage a lane keeps the half of its column sums on its side and adds
    its partner's copy of them, so lane 16 f + e ends with the geom-f sum of column e (45 instead of
    108 VALU instructions). */
-template <bool MD = false>
+/* XD (with MD): slots CAP..15 have no column. Their zero half is not added in the first stage, and lanes
+   CAP..15 of a row then end with sums of existing columns instead of zeros: for a caller that reads
+   the result at lanes below CAP only (update_constraint_lane: a dof's depth). Lanes below CAP never
+   see those slots: the half-row stage takes slots 4..7 from lanes 0..7 (side 0 of the first stage,
+   bank 1) for its bank 1, lanes 8..11 keep slots 0..3, and lanes 12..15 are a quad of their own in
+   the two quad stages. XD & 2: dpp_hi4_half_sel (the next stage is in the select form) */
+template <bool MD = false, int XD = 0>
 __device__ __forceinline__ float colsum16_pre(const float jr[CAP], float fr) {
   float q[16];
   {
@@ -3080,10 +3114,16 @@ __device__ __forceinline__ float colsum16_pre(const float jr[CAP], float fr) {
       /* side bits 3 and 2 are DPP banks (dpp_hi8_mirror) */
 #pragma unroll
       for (int k = 0; k < 8; k++) u8[k] = q[k] + dppf<0x140>(q[k]);
-      dpp_hi8_mirror(u8, q + 8);
+      if constexpr ((XD & 1) != 0) {
+        static_assert(CAP == 12, "slots 8..11 are the hi half of slots 0..3, slots 4..7 have none");
+        dpp_hi4_mirror(u8, q + 8);
+      } else {
+        dpp_hi8_mirror(u8, q + 8);
+      }
 #pragma unroll
       for (int k = 0; k < 4; k++) u4[k] = u8[k] + dppf<0x141>(u8[k]);
-      dpp_hi4_half(u4, u8 + 4);
+      if constexpr ((XD & 2) != 0) dpp_hi4_half_sel(u4, u8 + 4);
+      else dpp_hi4_half(u4, u8 + 4);
     } else {
       const bool s1 = li >= 8;
 #pragma unroll
@@ -3114,7 +3154,7 @@ __device__ __forceinline__ float colsum16(JP Jrow, float fr) {
 /* ZL: solve_cg's copies. The caller's qacc, qs, fs and Ma are exact zeros on the lanes past the dofs,
    whose share of the Gauss cost then needs no mask; the Newton kernels keep the masked forms (their
    direction is not shown to be zero there, and their code stays what it was) */
-template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false>
+template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false, int XD = 0>
 __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, const float jr[CAP], float qacc,
                                                        float qs, float fs, float Ma, float& grad) {
   const int ddep = vopq(c.ddep);
@@ -3208,7 +3248,7 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
     }
   }
   /* J'f per dof: a dof adds the column sum at its depth of every geom whose chain holds it */
-  const float colsum = colsum16_pre<MD>(jr, (ZL || r.ex) ? r.f : 0.f); /* ZL: 0 for a row that does not exist (above) */
+  const float colsum = colsum16_pre<MD, MD ? XD : 0>(jr, (ZL || r.ex) ? r.f : 0.f); /* ZL: 0 for a row that does not exist (above) */
   const float so = tsh(colsum, ddep), sx = tsh(colsum, 16 + ddep);
   tsync();
   float qc = 0.f;
@@ -3237,10 +3277,10 @@ __device__ __forceinline__ float update_constraint_lane(const Ctx& c, Rows& r, c
   grad = Ma - fs - qc;
   return cost;
 }
-template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false>
+template <int XG, bool XA = true, bool HS = true, bool ZL = false, bool MD = false, int XD = 0>
 __device__ __forceinline__ float update_constraint(const Ctx& c, Rows& r, const float jr[CAP], float qacc, float qs,
                                                   float fs, float Ma, float& grad) {
-  return tsum(update_constraint_lane<XG, XA, HS, ZL, MD>(c, r, jr, qacc, qs, fs, Ma, grad));
+  return tsum(update_constraint_lane<XG, XA, HS, ZL, MD, XD>(c, r, jr, qacc, qs, fs, Ma, grad));
 }
 
 /* G_f = sum_{r in foot f} D_r J_r J_r' (depth-indexed 12x12) for both feet of
@@ -3848,7 +3888,7 @@ __device__ __forceinline__ float solve_newton(const Ctx& c, Rows& r, float qs, f
    forces, no implicit_damping reads ftot). The iteration at the cap then ends with its step.
    FOLD, GN: the masks folded into data (below; solve_prep's GN). forward() leaves them off for the
    few instantiations that spilled more vector registers with them. */
-template <int XG, bool XA = true, bool FOLD = true, bool GN = true, bool DS = false>
+template <int XG, bool XA = true, bool FOLD = true, bool GN = true, bool DS = false, int XD = 0>
 __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float fs, float w, int& iters, bool live,
                                           float DinvM, float& ftot, bool qacc_only) {
   CP cfg = c.cfg;
@@ -3930,7 +3970,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
      integrate's w = qacc with forward's masked qacc), hence x, Ma and the Gauss term; the rows'
      forces are added on dof lanes only (update_constraint_lane's qc), hence grad = Ma - fs - qc,
      mg = M^-1 grad and search = -mg + beta search, and every step keeps x, Ma there. */
-  float cost = update_constraint<XG, XA, false, FOLD, DS>(c, r, jr, x, qs, fs, Ma, grad);
+  float cost = update_constraint<XG, XA, false, FOLD, DS, XD>(c, r, jr, x, qs, fs, Ma, grad);
   STAMP(S_UPD0);
   float mg = solve_pre<GN>(c, grad);
   STAMP(S_SOLVE0);
@@ -3963,7 +4003,7 @@ __device__ __forceinline__ float solve_cg(const Ctx& c, Rows& r, float qs, float
     r.jf = __builtin_fmaf(alpha, search, r.jf);
     if (r.anyl) r.jl += alpha * (r.sl * search);
     const float oldcost = cost, gold = grad, mgold = mg;
-    const float cl = update_constraint_lane<XG, XA, false, FOLD, DS>(c, r, jr, x, qs, fs, Ma, grad);
+    const float cl = update_constraint_lane<XG, XA, false, FOLD, DS, XD>(c, r, jr, x, qs, fs, Ma, grad);
     STAMP(S_UPD);
     it++;
     /* MJX's order (solver.py: _update_gradient, then the Polak-Ribiere beta, then the termination
@@ -4039,6 +4079,16 @@ __device__ __forceinline__ void feetech(const Ctx& c, LaneS& ls) {
   ls.ptau = tau;
   ls.ctrl = tau;
 }
+
+/* colsum16_pre's XD: the headline kernel only, the default-fields CG copy of the
+   default model without implicit damping; every other instantiation keeps the parent's instructions.
+   Bits: 1 no zero half, 2 no pad behind the half-row adds. ZB_COLSUM_DIET picks the items of an A/B
+   build (scripts/ab_build.sh ... -DZB_COLSUM_DIET=n); the product has both. */
+#ifndef ZB_COLSUM_DIET
+#define ZB_COLSUM_DIET 3
+#endif
+template <int SOLVER, int XG, bool FQ, bool DS>
+constexpr int COLSUM_DIET = (SOLVER == ZB_SOLVER_CG && XG == 0 && !FQ && DS) ? ZB_COLSUM_DIET : 0;
 
 /* ------------------------------- full forward ------------------------------ */
 /* mj_forward (+ sensors if requested). Leaves qacc in ls.qacc, kinematics in B. */
@@ -4126,7 +4176,7 @@ __device__ __forceinline__ void forward(const Ctx& c, const EnvS& s, LaneS& ls, 
     auto solve = [&](auto xa) -> float {
       constexpr bool XA = decltype(xa)::value;
       return SOLVER == ZB_SOLVER_CG
-                 ? solve_cg<XG, XA, FOLD, GN, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
+                 ? solve_cg<XG, XA, FOLD, GN, DS, COLSUM_DIET<SOLVER, XG, FQ, DS>>(c, r, qs, fs, ls.w, it2, nrows > 0, DinvM, ft, !FQ && !with_sensors)
                  : solve_newton<XG, XA, DS>(c, r, qs, fs, ls.w, it2, nrows > 0, ft);
     };
     bool xa = false; /* wave-uniform: an extra bank has rows */
