@@ -5136,6 +5136,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
         }
         {
           bool bad = (c.l < NV) && !(isfinite(ls.q) && isfinite(ls.v));
+          /* the base pose is in EnvS, in no dof lane's q: a NaN height in the air reaches no velocity
+             (no contact, and M and the bias do not read the position), so it is tested by itself */
+          bad = bad || !isfinite(s.bp[0] + s.bp[1] + s.bp[2] + s.bq[0] + s.bq[1] + s.bq[2] + s.bq[3]);
           if (tmaxi(bad ? 1 : 0)) s.nanflag |= 1u; /* keeps bit 1 (select_bank2) */
         }
         bool fail;
@@ -5183,6 +5186,11 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
                     (out && a.obs_critic) ? a.obs_critic + eo * ZB_OBS_CRITIC : nullptr,
                     (out && a.obs_extra) ? a.obs_extra + eo * ZB_OBS_EXTRA : nullptr, cv);
       }
+      if constexpr (XG != 0) {
+        /* the ghost pass is discarded, its flags too: select_bank2 ran on the post-step pose, a pose
+           this env's own step never evaluates, so bits 1 and 2 go back to what the step left (below) */
+        if (ghost) s.nanflag = (s.nanflag & ~0x606u) | ((s.nanflag >> 8) & 6u);
+      }
       if (resetting || ghost) break;
       if (__ballot(done_reset) == 0ull) break;
       if (done_reset) {
@@ -5191,6 +5199,9 @@ __global__ __launch_bounds__(64, ZB_WAVES_PER_EU) void step_kernel(StepArgs a) {
         resetting = true;
       } else {
         ghost = true;
+        /* park bits 1 and 2 in bits 9 and 10 across the pass (no register held over forward()); the
+           word leaves the kernel with those clear */
+        if constexpr (XG != 0) s.nanflag |= (s.nanflag & 6u) << 8;
       }
     }
     if (partial) break;

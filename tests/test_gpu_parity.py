@@ -82,6 +82,7 @@ class MaxErr:
         self.over = set()  # envs over the bound in the last add() calls (cleared by take_over())
         self.exempted = set()  # (output, env, excess / tol) of boundary envs over the bound (add exempt=)
         self.kneed = {}  # output -> the largest budget + 1 slack multiples needed by an env (one step)
+        self.nonfinite = []  # outputs that held a NaN or an infinity in some add(): report() fails on any
 
     def add(self, key, got, ref, tol, rtol=0.0, ref64=None, loose_abs=None, sens=None, exempt=None):
         """Record |got - ref| against tol + rtol |ref| elementwise (rows = envs; asserted in
@@ -96,6 +97,10 @@ class MaxErr:
         got = np.asarray(got, np.float64)
         ref = np.asarray(ref, np.float64)
         d = np.abs(got - ref)
+        if not np.isfinite(got).all():
+            # a non-finite output is never within a bound, for an exempt env as little as for any other
+            envs = np.flatnonzero(~np.isfinite(np.atleast_1d(got)).reshape(np.atleast_1d(got).shape[0], -1).all(1))
+            self.nonfinite.append(f"{key}: non-finite output, envs {envs.tolist()}")
         slack = 0.0
         if ref64 is not None:
             gap = np.abs(ref - np.asarray(ref64, np.float64))
@@ -124,14 +129,15 @@ class MaxErr:
             kn = np.where(raw > 0, raw / np.maximum(gap.reshape(-1), 1e-30), 0.0)
             top = sorted(kn.tolist(), reverse=True)[:self.budget + 1]
             self.kneed[key] = max(self.kneed.get(key, [0.0]), top)
-        n_over = int((rows > tol).sum())
-        self.over |= set(np.nonzero(rows > tol)[0].tolist())
+        over = ~(rows <= tol)  # a NaN row is over (rows > tol is False for it)
+        n_over = int(over.sum())
+        self.over |= set(np.nonzero(over)[0].tolist())
         self.nout[key] = max(self.nout.get(key, 0), n_over)
         held = np.ones(rows.shape[0], bool)
         if exempt is not None and len(exempt):
             held[np.asarray(sorted(exempt), int)] = False
             for ex in sorted(exempt):
-                if rows[ex] > tol:
+                if not rows[ex] <= tol:
                     self.exempted.add((key, int(ex), float(rows[ex] / tol)))
         worst = float(rows[held].max()) if held.any() else 0.0
         lim = self.loose * tol if loose_abs is None else loose_abs
@@ -159,6 +165,7 @@ class MaxErr:
         if self.exempted:
             print(f"[{self.name}] budget envs whose step starts with a contact at its activation boundary (no loose "
                   "limit): " + ", ".join(f"{k} env {e} {x:.0f}x" for k, e, x in sorted(self.exempted)))
+        assert not self.nonfinite, f"{self.name}: " + "; ".join(self.nonfinite)
         assert not self.bad, f"{self.name}: " + "; ".join(self.bad)
 
 
