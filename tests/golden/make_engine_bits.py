@@ -1,6 +1,6 @@
 """Record the HIP engine's own output bits (needs the GPU): tests/golden/engine_bits_<case>.npz.
 
-    python tests/golden/make_engine_bits.py [--out DIR] [case ...]
+    python tests/golden/make_engine_bits.py [--out DIR] [--lib libzbot_hip.so] [case ...]
 
 The other goldens pin the CPU oracle, and the engine is held to them within a tolerance. These
 pin the engine itself, bit for bit, so that a change meant to leave every rounding alone (fewer
@@ -19,23 +19,22 @@ oracle-based tests first (tests/test_gpu_parity.py, tests/test_gpu_colliders.py)
 script on the GPU at that commit and commit the new files together with the change; main() refuses
 to write a case that lost what makes it worth having (an episode end, a solve below the iteration
 cap, second-bank rows, a contact in every extra contact-row bank of the case's kernel: bank_envs).
+What the engine-bit families share is in tests/bit_fixtures.py.
 """
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.dirname(HERE)):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/, when run as a script
+import bit_fixtures as F  # noqa: E402
+import collider_util as U  # noqa: E402
+from zbot_amd import default_config  # noqa: E402
 
+FAMILY, MAX_KB = "engine_bits", 300
 N = 64
 N_ODD = 3  # the first three envs again, alone
-SIGMA = 0.2
 
 CASES = {
     # (a) the headline kernel: CG, the default model
@@ -68,38 +67,15 @@ CASES = {
 BANKS_PRINTED_ONLY = ("cg_limbs", "cg_many", "cg_sole_pair")
 
 
-def case_model(model=None):
-    from zbot_amd import compile_model  # noqa: PLC0415
-
-    if model is None:
-        return compile_model()
-    if model in ("sole_pair", "limbs_pair", "many_pair"):
-        import collider_util as U  # noqa: PLC0415
-
-        return compile_model(getattr(U, model + "_desc")())
-    from zbot_amd.mjcf import load_mjcf  # noqa: PLC0415
-
-    return compile_model(load_mjcf(os.path.join(ROOT, "ksim-gym-zbot_amd", "assets", model)))
-
-
-def case_noise(steps, seed):
-    """[steps, N, 20] int8: N(0, 1) in steps of 1/32 (what the fixture keeps of its actions)."""
-    z = np.random.default_rng(seed).standard_normal((steps, N, 20))
-    return np.clip(np.rint(z * 32.0), -127, 127).astype(np.int8)
-
-
-def case_actions(cm, noise_q):
-    """[steps, N, 20] float32: the joint biases + SIGMA N(0, 1), exact in float32 from the int8 noise."""
-    bias = np.array([cm.cmodel.joint_bias[i] for i in range(20)], np.float32)
-    return bias + np.float32(SIGMA) * (noise_q.astype(np.float32) / np.float32(32.0))
+def inputs(name):
+    kw = CASES[name]
+    return {"noise_q": F.action_noise(kw["seed"], kw["steps"], N)}
 
 
 def start_qpos(cm, start, seed):
     """[N, 27] qpos of a case that does not start from the reset state (None: it does)."""
     if start is None:
         return None
-    import collider_util as U  # noqa: PLC0415
-
     if start == "touching":
         return U.touching_states(cm, N, seed).astype(np.float32)
     if start == "crossing_touching":
@@ -109,8 +85,6 @@ def start_qpos(cm, start, seed):
 
 def second_bank_envs(cm, qpos) -> int:
     """Envs whose start state has a floor contact on a collider beyond the two soles."""
-    import collider_util as U  # noqa: PLC0415
-
     return sum(any(len(cons) > 0 for cons in U.contacts(cm, q.astype(np.float64))[2:]) for q in qpos)
 
 
@@ -123,8 +97,6 @@ def bank_envs(cm, cfg, qpos) -> list[tuple[str, int]]:
     when the oracle's constraint rows hold a contact row without root columns (the pair's only).
     The oracle is the repository's own CPU one (oracle/oracle.py, its libraries built by
     __graft_entry__.build() or on first use by oracle.build()); nothing outside the tree is read."""
-    import collider_util as U  # noqa: PLC0415
-
     m = cm.cmodel
     q64 = [q.astype(np.float64) for q in qpos]
     out = []
@@ -135,68 +107,34 @@ def bank_envs(cm, cfg, qpos) -> list[tuple[str, int]]:
             out.append((f"floor bank {b + 1}", sum(any(len(con[e][g]) > 0 for g in cand[e][2 * b:2 * b + 2])
                                                    for e in range(len(q64)))))
     if m.npair:
-        sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O  # noqa: PLC0415
 
         O.build()
-        rows = [O.constraint_problem(m, cfg, q, np.zeros(26, np.float32), precision="f64") for q in qpos]
+        rows = [O.constraint_problem(m, cfg, q, np.zeros(cm.nv, np.float32), precision="f64") for q in qpos]
         out.append(("sole pair", sum(bool(((p["type"] == 2) & (np.abs(p["J"][:, :6]).max(1) == 0)).any()) for p in rows)))
     return out
 
 
-def run_engine(cm, cfg, n, seed, actions, qpos):
-    """One engine of the first n envs through every step; the arrays a fixture keeps."""
-    import torch  # noqa: PLC0415
-    from zbot_amd import cstructs as cs  # noqa: PLC0415
-    from zbot_amd.engine import HipEngine  # noqa: PLC0415
-
-    eng = HipEngine(cm, cfg, n, seed=seed)
-    eng.reset()
-    if qpos is not None:
-        st = eng.get_state().cpu().numpy()
-        st[:, :27] = qpos[:n]
-        st[:, 32:58] = 0.0
-        st[:, cs.S_QACCW:cs.S_QACCW + 32] = 0.0
-        eng.set_state(torch.from_numpy(st))
-    rows = {"reward": [], "done": [], "success": [], "solver_iters": []}
-    out = None
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[:n])).cuda())
-        torch.cuda.synchronize()
-        for k in ("reward", "done", "success"):
-            rows[k].append(out[k].cpu().numpy().copy())
-        rows["solver_iters"].append(eng.solver_iters().cpu().numpy())  # of this launch
-    d = {k: np.stack(v) for k, v in rows.items()}
-    d["final_state"] = eng.get_state().cpu().numpy()
-    d["final_rand"] = eng.get_rand().cpu().numpy()
-    for k, v in out.items():
-        d[f"last_{k}"] = v.cpu().numpy().copy()
-    return d
-
-
-def run_case(name, noise_q=None):
+def run_case(name, noise_q=None, lib_path=None):
     """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
-    kw = dict(CASES[name])
-    from zbot_amd import default_config  # noqa: PLC0415
-
-    cm = case_model(kw.get("model"))
+    kw = CASES[name]
+    cm = F.model(kw.get("model"))
     cfg = default_config(solver=kw.get("solver", "cg"), eulerdamp=kw.get("eulerdamp", False),
                          push=kw.get("push", False), randomize=kw.get("randomize", False))
     if noise_q is None:
-        noise_q = case_noise(kw["steps"], kw["seed"])
-    actions = case_actions(cm, noise_q)
+        noise_q = inputs(name)["noise_q"]
     qpos = start_qpos(cm, kw.get("start"), kw["seed"])
     data = {"noise_q": noise_q}
     for tag, n in (("", N), ("odd_", N_ODD)):
-        for k, v in run_engine(cm, cfg, n, kw["seed"], actions, qpos).items():
-            data[tag + k] = v
+        data.update(F.tagged(tag, F.run(cm, cfg, n, kw["seed"], F.actions(cm, noise_q), start=F.rest_at(cm, qpos),
+                                        lib_path=lib_path, final=("final_state", "final_rand", "last"))))
     return data, cm, cfg, qpos
 
 
 def check_case(name, data, cm, cfg, qpos) -> None:
     """What makes the fixture worth having, on the run that is about to be recorded."""
     kw = CASES[name]
-    assert np.isfinite(data["final_state"][:, :58]).all(), f"{name}: non-finite state"
+    assert np.isfinite(data["final_state"][:, F.motion_cols(cm)]).all(), f"{name}: non-finite state"
     if name == "cg":
         # a control step: n_substeps solves of at most cfg.iterations iterations (a reset pass adds one)
         cap = cfg.n_substeps * cfg.iterations
@@ -216,23 +154,5 @@ def check_case(name, data, cm, cfg, qpos) -> None:
             assert all(k >= 1 for _, k in banks), f"{name}: a bank of its kernel stays empty ({banks})"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
-    ap.add_argument("--out", default=HERE)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in CASES:
-        if a.cases and name not in a.cases:
-            continue
-        data, cm, cfg, qpos = run_case(name)
-        check_case(name, data, cm, cfg, qpos)
-        path = os.path.join(a.out, f"engine_bits_{name}.npz")
-        np.savez_compressed(path, **data)
-        kb = os.path.getsize(path) / 1024
-        assert kb < 300, f"{path}: {kb:.0f} KB"
-        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
-
-
 if __name__ == "__main__":
-    main()
+    F.main(sys.modules[__name__])

@@ -30,24 +30,20 @@ one, or the limit row is missing.
 
 The fixtures were recorded with the library of commit 132bf6a ("Velocity commands: UnifiedCommand
 and tracking rewards in step kernel"), the parent of the change that cut the CG wave's non-VALU
-issue slots, before any kernel edit.
+issue slots, before any kernel edit. What the engine-bit families share is in tests/bit_fixtures.py.
 """
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.join(ROOT, "oracle"), os.path.dirname(HERE), HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/, when run as a script
+import bit_fixtures as F  # noqa: E402
+import collider_util as U  # noqa: E402
+from zbot_amd import default_config  # noqa: E402
 
-import make_engine_bits as G  # noqa: E402
-import make_smooth_bits as S  # noqa: E402
-
+FAMILY, MAX_KB = "slot_diet", 100
 STEPS = 3
 LIMIT_JOINT = ("left_elbow_roll", 1)  # env B: past the upper bound
 VEL_SIGMA = 1.0  # rad/s, in steps of 1/32
@@ -62,88 +58,52 @@ CASES["generic_cg"] = dict(seed=67, solver="cg", layout="AB", plain=True, iterat
 
 
 def case_cfg(kw):
-    from zbot_amd import default_config  # noqa: PLC0415
-
     extra = dict(obs_noise=False, autoreset=False) if kw.get("plain") else {}
     if "iterations" in kw:
         extra["iterations"] = kw["iterations"]
     return default_config(solver=kw["solver"], **extra)
 
 
-def case_noise(kw):
-    z = np.random.default_rng(kw["seed"]).standard_normal((STEPS, len(kw["layout"]), 20))
-    return np.clip(np.rint(z * 32.0), -127, 127).astype(np.int8)
+def inputs(name):
+    kw = CASES[name]
+    return {"noise_q": F.action_noise(kw["seed"], STEPS, len(kw["layout"]))}
 
 
 def start_state(cm, kw, st):
     """Reset state rows `st` [n, S_END] moved to the case's start: hinge velocities for every env,
     A lifted, B with one hinge past its limit; the warm start zero."""
-    import collider_util as U  # noqa: PLC0415
-    from zbot_amd import cstructs as cs  # noqa: PLC0415
-
     st = st.copy()
     n = len(kw["layout"])
-    z = np.random.default_rng(kw["seed"] + 1000).standard_normal((n, 20))
-    vel = (np.float32(VEL_SIGMA) * np.clip(np.rint(z * 32.0), -127, 127).astype(np.float32) / np.float32(32.0))
+    vel = np.float32(VEL_SIGMA) * F.noise(kw["seed"] + 1000, (n, 20)).astype(np.float32) / np.float32(32.0)
     for e, kind in enumerate(kw["layout"]):
         st[e] = st[0]  # the same reset row for every env: A and B differ only as described
-        st[e, 32:58] = 0.0
-        st[e, 38:58] = vel[e]
+        F.at_rest(cm, st[e])
+        st[e, F.qvel_cols(cm)][6:] = vel[e]  # past the free joint's six dofs
         if kind == "A":
-            st[e, 2] += np.float32(LIFT)
+            F.lift(st[e], LIFT)
         else:
-            b = S.hinge(cm, LIMIT_JOINT[0])
-            st[e, b.qposadr] = np.float32(b.jrange[1] + S.PAST)
+            F.set_past(cm, st[e], *LIMIT_JOINT)
             # down to the floor: the soles' lowest point 1 mm below it
-            st[e, 2] -= np.float32(U.lowest_point(cm, st[e, :27].astype(np.float64)) + 1e-3)
-    st[:, cs.S_QACCW:cs.S_QACCW + 32] = 0.0
+            F.lift(st[e], -(U.lowest_point(cm, st[e, F.qpos_cols(cm)].astype(np.float64)) + 1e-3))
     return st
 
 
-def run_engine(cm, cfg, kw, actions, lib_path=None, swap=False):
-    """One engine through the case's steps; the arrays a fixture keeps. swap: envs in reverse order
-    (state rows, randomization rows and actions), the results reversed back."""
-    import torch  # noqa: PLC0415
-    from zbot_amd.engine import HipEngine  # noqa: PLC0415
-
-    n = len(kw["layout"])
-    eng = HipEngine(cm, cfg, n, seed=kw["seed"], lib_path=lib_path)
-    eng.reset()
-    st = start_state(cm, kw, eng.get_state().cpu().numpy())
-    rnd = eng.get_rand().cpu().numpy()
-    rnd[:] = rnd[0]
-    o = slice(None, None, -1) if swap else slice(None)
-    eng.set_state(torch.from_numpy(np.ascontiguousarray(st[o])))
-    eng.set_rand(torch.from_numpy(np.ascontiguousarray(rnd[o])))
-    rows = {"reward": [], "done": [], "success": [], "solver_iters": [], "states": []}
-    out = None
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[o])).cuda())
-        torch.cuda.synchronize()
-        for k in ("reward", "done", "success"):
-            rows[k].append(out[k].cpu().numpy()[o].copy())
-        rows["solver_iters"].append(eng.solver_iters().cpu().numpy()[o].copy())
-        rows["states"].append(eng.get_state().cpu().numpy()[o].copy())
-    d = {k: np.stack(v) for k, v in rows.items()}
-    d["start_state"] = st
-    d["start_rand"] = rnd
-    for k, v in out.items():
-        d[f"last_{k}"] = v.cpu().numpy()[o].copy()
-    return d
+def run_layout(cm, kw, noise_q, start, same_rand, lib_path=None, swap=False):
+    """One engine of the case's layout through its steps, from start(cm, kw, reset rows); the arrays a
+    fixture keeps. same_rand: every env gets randomization row 0 (else its own)."""
+    data = {"noise_q": noise_q}
+    data.update(F.run(cm, case_cfg(kw), len(kw["layout"]), kw["seed"], F.actions(cm, noise_q),
+                      start=lambda st: start(cm, kw, st), rand="row0" if same_rand else "own", lib_path=lib_path,
+                      swap=swap, per_step=(*F.PER_STEP, "states"), final=("start_state", "start_rand", "last")))
+    return data
 
 
 def run_case(name, noise_q=None, lib_path=None, swap=False):
     """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
-    from zbot_amd import compile_model  # noqa: PLC0415
-
-    kw = CASES[name]
-    cm = compile_model()
+    cm = F.model()
     if noise_q is None:
-        noise_q = case_noise(kw)
-    actions = G.case_actions(cm, noise_q)
-    data = {"noise_q": noise_q}
-    data.update(run_engine(cm, case_cfg(kw), kw, actions, lib_path=lib_path, swap=swap))
-    return data, cm
+        noise_q = inputs(name)["noise_q"]
+    return run_layout(cm, CASES[name], noise_q, start_state, True, lib_path, swap), cm
 
 
 def row_zones(cm, cfg, q, v):
@@ -162,21 +122,14 @@ def row_zones(cm, cfg, q, v):
 
 def twin_zones(name, cm, data):
     """[STEPS, n, 5] row_zones of the CPU twin's pre-step states along the case's actions."""
-    import oracle as O  # noqa: PLC0415
-
-    O.build()
     kw = CASES[name]
     cfg = case_cfg(kw)
     n = len(kw["layout"])
-    env = O.OracleEnv(cm.cmodel, cfg, n, seed=kw["seed"])
-    env.reset()
-    env.state[:] = data["start_state"]
-    env.rand[:] = data["start_rand"]
-    actions = G.case_actions(cm, data["noise_q"])
+    _, env, actions = F.cpu_twin(cm, cfg, kw["seed"], data)
     z = np.zeros((STEPS, n, 5), np.int64)
     for t in range(STEPS):
         for e in range(n):
-            z[t, e] = row_zones(cm, cfg, env.state[e, :27], env.state[e, 32:58])
+            z[t, e] = row_zones(cm, cfg, env.state[e, F.qpos_cols(cm)], env.state[e, F.qvel_cols(cm)])
         env.step(actions[t])
     return z
 
@@ -205,31 +158,12 @@ def check_zones(name, cm, data) -> None:
 
 def check_case(name, data, cm, zones=True) -> None:
     """What makes the fixture worth having, on the run that is about to be recorded (or replayed)."""
-    assert np.isfinite(data["states"][:, :, :58]).all(), f"{name}: non-finite state"
+    assert np.isfinite(data["states"][:, :, F.motion_cols(cm)]).all(), f"{name}: non-finite state"
     assert (data["solver_iters"] > 0).all(), f"{name}: a step without a solver iteration"
     assert not data["done"].any(), f"{name}: an env terminated"
     if zones:
         check_zones(name, cm, data)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
-    ap.add_argument("--out", default=HERE)
-    ap.add_argument("--lib", default=None, help="the library to record with (default: the product build)")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in CASES:
-        if a.cases and name not in a.cases:
-            continue
-        data, cm = run_case(name, lib_path=a.lib and os.path.abspath(a.lib))
-        check_case(name, data, cm)
-        path = os.path.join(a.out, f"slot_diet_{name}.npz")
-        np.savez_compressed(path, **data)
-        kb = os.path.getsize(path) / 1024
-        assert kb < 100, f"{path}: {kb:.0f} KB"
-        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
-
-
 if __name__ == "__main__":
-    main()
+    F.main(sys.modules[__name__])

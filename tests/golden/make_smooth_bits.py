@@ -1,7 +1,7 @@
 """Record the HIP engine's bits on two paths the engine_bits fixtures do not reach (needs the GPU):
 tests/golden/smooth_bits_<case>.npz.
 
-    python tests/golden/make_smooth_bits.py [--out DIR] [case ...]
+    python tests/golden/make_smooth_bits.py [--out DIR] [--lib libzbot_hip.so] [case ...]
 
 make_engine_bits.py pins the engine on walking and touching robots. By construction those runs
 have contact rows in every wave and no joint past its range, so two paths of the once-per-substep
@@ -28,28 +28,24 @@ Every case runs four control steps with n = 2 and again with n = 3 (the second w
 is the ghost copy past n), with the CG and the Newton kernels. It keeps what make_engine_bits.py
 keeps. main() refuses to write a case whose premise fails; both premises are checked on the CPU
 (tests/collider_util.contacts() is empty for an airborne start; the chosen dof is limited and its
-start angle lies outside its range).
+start angle lies outside its range). What the engine-bit families share is in tests/bit_fixtures.py.
 """
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.dirname(HERE), HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/, when run as a script
+import bit_fixtures as F  # noqa: E402
+import collider_util as U  # noqa: E402
+from zbot_amd import default_config  # noqa: E402
 
-import make_engine_bits as G  # noqa: E402
-
+FAMILY, MAX_KB = "smooth_bits", 300
 STEPS = 4
 SIZES = (("", 2), ("odd_", 3))
 N = 3  # envs of the largest engine
 LIFT = 0.5  # m above the reset height
-PAST = 0.05  # rad past the range
 # env -> (joint, +1: past the upper bound, -1: past the lower one)
 LIMIT_JOINTS = (("left_elbow_roll", 1), ("right_shoulder_roll", -1), ("right_knee_pitch", 1))
 
@@ -62,55 +58,35 @@ for _sv in ("cg", "newton"):
     CASES[f"airmix_{_sv}_nofloss"] = dict(seed=35, solver=_sv, start="airmix", nofloss=True)
 
 
-def case_model(nofloss=False):
-    from zbot_amd import compile_model  # noqa: PLC0415
-    from zbot_amd.model import load_description  # noqa: PLC0415
-
-    if not nofloss:
-        return compile_model()
-    d = load_description()
-    for sc in d["servo_classes"].values():
-        sc["frictionloss"] = 0.0
-    return compile_model(d)
+def inputs(name):
+    return {"noise_q": F.action_noise(CASES[name]["seed"], STEPS, N)}
 
 
 def airborne(start, e) -> bool:
     return start == "air" or (start == "airmix" and e % 2 == 0)
 
 
-def hinge(cm, joint):
-    return next(b for b in cm.bodies if b.jnt_name == joint)
-
-
 def start_state(cm, start, st):
     """The reset state rows `st` [n, S_END] moved to the case's start (velocities and warm start zero)."""
-    from zbot_amd import cstructs as cs  # noqa: PLC0415
-
     st = st.copy()
     for e in range(st.shape[0]):
         if start == "limit":
-            joint, side = LIMIT_JOINTS[e]
-            b = hinge(cm, joint)
-            st[e, b.qposadr] = np.float32(b.jrange[1] + PAST if side > 0 else b.jrange[0] - PAST)
+            F.set_past(cm, st[e], *LIMIT_JOINTS[e])
         elif airborne(start, e):
-            st[e, 2] += np.float32(LIFT)
-    st[:, 32:58] = 0.0
-    st[:, cs.S_QACCW:cs.S_QACCW + 32] = 0.0
-    return st
+            F.lift(st[e], LIFT)
+    return F.at_rest(cm, st)
 
 
 def check_start(name, cm, st) -> None:
     """The case's premise on the start state, on the CPU."""
-    import collider_util as U  # noqa: PLC0415
-
     kw = CASES[name]
     m = cm.cmodel
     for e in range(st.shape[0]):
-        q = st[e, :27].astype(np.float64)
+        q = st[e, F.qpos_cols(cm)].astype(np.float64)
         ncon = sum(len(cons) for cons in U.contacts(cm, q, margin=float(m.floor_margin)))
         if kw["start"] == "limit":
             joint, side = LIMIT_JOINTS[e]
-            b = hinge(cm, joint)
+            b = F.hinge(cm, joint)
             d = b.dofadr
             assert m.dof_limited[d] == 1, f"{name}: {joint} is not limited"
             lo, hi = float(m.dof_range[d][0]), float(m.dof_range[d][1])
@@ -128,51 +104,18 @@ def check_start(name, cm, st) -> None:
         assert all(float(m.dof_frictionloss[d]) == 0.0 for d in range(cm.nv)), f"{name}: friction loss left"
 
 
-def run_engine(cm, cfg, n, seed, actions, start):
-    """One engine of n envs from the case's start through every step; the arrays a fixture keeps."""
-    import torch  # noqa: PLC0415
-    from zbot_amd.engine import HipEngine  # noqa: PLC0415
-
-    eng = HipEngine(cm, cfg, n, seed=seed)
-    eng.reset()
-    st = start_state(cm, start, eng.get_state().cpu().numpy())
-    eng.set_state(torch.from_numpy(st))
-    rows = {"reward": [], "done": [], "success": [], "solver_iters": []}
-    out = None
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[:n])).cuda())
-        torch.cuda.synchronize()
-        for k in ("reward", "done", "success"):
-            rows[k].append(out[k].cpu().numpy().copy())
-        rows["solver_iters"].append(eng.solver_iters().cpu().numpy())
-    d = {k: np.stack(v) for k, v in rows.items()}
-    d["start_state"] = st
-    d["final_state"] = eng.get_state().cpu().numpy()
-    d["final_rand"] = eng.get_rand().cpu().numpy()
-    for k, v in out.items():
-        d[f"last_{k}"] = v.cpu().numpy().copy()
-    return d
-
-
-def case_noise(seed):
-    z = np.random.default_rng(seed).standard_normal((STEPS, N, 20))
-    return np.clip(np.rint(z * 32.0), -127, 127).astype(np.int8)
-
-
-def run_case(name, noise_q=None):
+def run_case(name, noise_q=None, lib_path=None):
     """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
-    from zbot_amd import default_config  # noqa: PLC0415
-
     kw = CASES[name]
-    cm = case_model(kw.get("nofloss", False))
+    cm = F.model("nofloss" if kw.get("nofloss") else None)
     cfg = default_config(solver=kw["solver"], autoreset=kw["start"] == "limit")
     if noise_q is None:
-        noise_q = case_noise(kw["seed"])
-    actions = G.case_actions(cm, noise_q)
+        noise_q = inputs(name)["noise_q"]
     data = {"noise_q": noise_q}
     for tag, n in SIZES:
-        for k, v in run_engine(cm, cfg, n, kw["seed"], actions, kw["start"]).items():
-            data[tag + k] = v
+        data.update(F.tagged(tag, F.run(cm, cfg, n, kw["seed"], F.actions(cm, noise_q), lib_path=lib_path,
+                                        start=lambda st: start_state(cm, kw["start"], st),
+                                        final=("start_state", "final_state", "final_rand", "last"))))
     return data, cm
 
 
@@ -180,7 +123,7 @@ def check_case(name, data, cm) -> None:
     """What makes the fixture worth having, on the run that is about to be recorded."""
     kw = CASES[name]
     for tag, _ in SIZES:
-        assert np.isfinite(data[tag + "final_state"][:, :58]).all(), f"{name}: non-finite state"
+        assert np.isfinite(data[tag + "final_state"][:, F.motion_cols(cm)]).all(), f"{name}: non-finite state"
         check_start(name, cm, data[tag + "start_state"])
         it = data[tag + "solver_iters"]
         print(f"  {name} {tag or 'n2_'}solver_iters per step: {it.tolist()}")
@@ -192,23 +135,5 @@ def check_case(name, data, cm) -> None:
             assert (it[:, ~air] > 0).all(), f"{name}: an env on the floor ran no solver iteration"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
-    ap.add_argument("--out", default=HERE)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in CASES:
-        if a.cases and name not in a.cases:
-            continue
-        data, cm = run_case(name)
-        check_case(name, data, cm)
-        path = os.path.join(a.out, f"smooth_bits_{name}.npz")
-        np.savez_compressed(path, **data)
-        kb = os.path.getsize(path) / 1024
-        assert kb < 300, f"{path}: {kb:.0f} KB"
-        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
-
-
 if __name__ == "__main__":
-    main()
+    F.main(sys.modules[__name__])

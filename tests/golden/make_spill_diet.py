@@ -45,25 +45,20 @@ problems in float32 and with its servo torques, and may take an evaluation more 
 
 The fixtures were recorded with the library of commit 57ba670 ("Policy shape per handle: GRU depth
 and mixture count in HIP"), the parent of the change to the line search's exit path, before any
-kernel edit.
+kernel edit. What the engine-bit families share is in tests/bit_fixtures.py.
 """
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.join(ROOT, "oracle"), os.path.dirname(HERE), HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/, when run as a script
+import bit_fixtures as F  # noqa: E402
+import make_slot_diet as D  # noqa: E402  (the A and B rows, the pair's config, the layout's run)
+from zbot_amd import cstructs as cs  # noqa: E402
 
-import make_engine_bits as G  # noqa: E402
-import make_slot_diet as D  # noqa: E402
-import make_smooth_bits as S  # noqa: E402
-
+FAMILY, MAX_KB = "spill_diet", 100
 STEPS = 3
 HIGH = 0.5  # m above the reset height: past the task's height bound
 
@@ -79,50 +74,36 @@ for _kw in CASES.values():
     _kw["solver"] = "cg"
 SWAPPED = [n for n, kw in CASES.items() if kw.get("plain") and len(kw["layout"]) == 2]
 
-_models = {}
 
 
 def case_model(kw):
-    key = bool(kw.get("nogravity"))
-    if key not in _models:
-        from zbot_amd import compile_model  # noqa: PLC0415
-
-        if key:
-            from zbot_amd.model import load_description  # noqa: PLC0415
-
-            d = load_description()
-            d.setdefault("option", {})["gravity"] = [0.0, 0.0, 0.0]
-            _models[key] = compile_model(d)
-        else:
-            _models[key] = compile_model()
-    return _models[key]
+    return F.model("nogravity" if kw.get("nogravity") else None)
 
 
-def case_noise(kw):
-    q = D.case_noise(dict(kw, layout=kw["layout"]))
+def inputs(name):
+    kw = CASES[name]
+    q = F.action_noise(kw["seed"], STEPS, len(kw["layout"]))
     for e, kind in enumerate(kw["layout"]):
         if kind == "F":
             q[:, e] = 0  # the held target: the joint biases themselves
-    return q
+    return {"noise_q": q}
 
 
 def start_state(cm, kw, st):
     """Reset state rows `st` moved to the case's start. A, B: make_slot_diet.start_state. H: B lifted
     HIGH. F: at rest 0.1 m above the reset height, every hinge and its servo's plan at the joint bias
     (the action of zero noise), the warm start zero."""
-    from zbot_amd import cstructs as cs  # noqa: PLC0415
-
     lay = kw["layout"]
     out = D.start_state(cm, dict(kw, layout="".join("A" if k == "A" else "B" for k in lay)), st)
     m = cm.cmodel
     for e, kind in enumerate(lay):
         if kind == "H":
-            out[e, 2] += np.float32(HIGH)
+            F.lift(out[e], HIGH)
         elif kind == "F":
             out[e] = st[0]
-            out[e, 2] += np.float32(D.LIFT)
-            out[e, 32:64] = 0.0
-            out[e, cs.S_QACCW:cs.S_QACCW + 32] = 0.0
+            F.lift(out[e], D.LIFT)
+            out[e, cs.S_QVEL:cs.S_QACCW] = 0.0
+            out[e, cs.S_QACCW:cs.S_PLAN_POS] = 0.0
             for a in range(m.nu):
                 tgt = np.float32(m.joint_bias[a])
                 out[e, m.dof_qposadr[m.act_dof[a]]] = tgt
@@ -132,53 +113,14 @@ def start_state(cm, kw, st):
     return out
 
 
-def run_engine(cm, cfg, kw, actions, lib_path=None, swap=False):
-    """make_slot_diet.run_engine with this module's start states; a case that is not `plain` keeps
-    every env's own randomization row."""
-    import torch  # noqa: PLC0415
-    from zbot_amd.engine import HipEngine  # noqa: PLC0415
-
-    n = len(kw["layout"])
-    eng = HipEngine(cm, cfg, n, seed=kw["seed"], lib_path=lib_path)
-    eng.reset()
-    st = start_state(cm, kw, eng.get_state().cpu().numpy())
-    rnd = eng.get_rand().cpu().numpy()
-    if kw.get("plain"):
-        rnd[:] = rnd[0]
-    o = slice(None, None, -1) if swap else slice(None)
-    eng.set_state(torch.from_numpy(np.ascontiguousarray(st[o])))
-    eng.set_rand(torch.from_numpy(np.ascontiguousarray(rnd[o])))
-    rows = {"reward": [], "done": [], "success": [], "solver_iters": [], "states": []}
-    out = None
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[o])).cuda())
-        torch.cuda.synchronize()
-        for k in ("reward", "done", "success"):
-            rows[k].append(out[k].cpu().numpy()[o].copy())
-        rows["solver_iters"].append(eng.solver_iters().cpu().numpy()[o].copy())
-        rows["states"].append(eng.get_state().cpu().numpy()[o].copy())
-    d = {k: np.stack(v) for k, v in rows.items()}
-    d["start_state"] = st
-    d["start_rand"] = rnd
-    for k, v in out.items():
-        d[f"last_{k}"] = v.cpu().numpy()[o].copy()
-    return d
-
-
-def case_cfg(kw):
-    return D.case_cfg(kw)
-
-
 def run_case(name, noise_q=None, lib_path=None, swap=False):
-    """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
+    """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay). A case
+    that is not `plain` keeps every env's own randomization row."""
     kw = CASES[name]
     cm = case_model(kw)
     if noise_q is None:
-        noise_q = case_noise(kw)
-    actions = G.case_actions(cm, noise_q)
-    data = {"noise_q": noise_q}
-    data.update(run_engine(cm, case_cfg(kw), kw, actions, lib_path=lib_path, swap=swap))
-    return data, cm
+        noise_q = inputs(name)["noise_q"]
+    return D.run_layout(cm, kw, noise_q, start_state, bool(kw.get("plain")), lib_path, swap), cm
 
 
 # ---- the CPU twin's line searches ----
@@ -296,24 +238,17 @@ def ls_counts(p, qaccw, cfg, meaninertia):
 def twin(name, data):
     """The CPU twin along the case: (counts[t][e]: ls_counts of the pre-step states; rows [STEPS, n, 2]:
     limit rows and contact rows there; done [STEPS, n])."""
-    import oracle as O  # noqa: PLC0415
-    from zbot_amd import cstructs as cs  # noqa: PLC0415
-
-    O.build()
     kw = CASES[name]
-    cm, cfg = case_model(kw), case_cfg(kw)
+    cm, cfg = case_model(kw), D.case_cfg(kw)
     n = len(kw["layout"])
-    env = O.OracleEnv(cm.cmodel, cfg, n, seed=kw["seed"])
-    env.reset()
-    env.state[:, :data["start_state"].shape[1]] = data["start_state"]
-    env.rand[:] = data["start_rand"]
-    actions = G.case_actions(cm, data["noise_q"])
+    O, env, actions = F.cpu_twin(cm, cfg, kw["seed"], data)
     counts, rows, done = [], np.zeros((STEPS, n, 2), np.int64), np.zeros((STEPS, n), bool)
     for t in range(STEPS):
         row = []
         for e in range(n):
             w = env.state[e, cs.S_QACCW:cs.S_QACCW + cm.nv]
-            p = O.constraint_problem(cm.cmodel, cfg, env.state[e, :27], env.state[e, 32:58], qaccw=w, precision="f32")
+            p = O.constraint_problem(cm.cmodel, cfg, env.state[e, F.qpos_cols(cm)], env.state[e, F.qvel_cols(cm)], qaccw=w,
+                                     precision="f32")
             row.append(ls_counts(p, w, cfg, float(cm.cmodel.meaninertia)))
             rows[t, e] = int((p["type"] == 1).sum()), int((p["type"] == 2).sum())
         counts.append(row)
@@ -380,7 +315,7 @@ def check_all(held, differ, sizes) -> None:
 def check_case(name, data) -> None:
     """On the run that is about to be recorded (or replayed): finite, and the recorded flags."""
     kw = CASES[name]
-    assert np.isfinite(data["states"][:, :, :58]).all(), f"{name}: non-finite state"
+    assert np.isfinite(data["states"][:, :, F.motion_cols(case_model(kw))]).all(), f"{name}: non-finite state"
     for e, kind in enumerate(kw["layout"]):
         if kind == "H":
             assert data["done"][0, e], f"{name}: env {e} (H) did not terminate at the first control step"
@@ -392,28 +327,16 @@ def check_case(name, data) -> None:
             assert (data["solver_iters"][:, e] > 0).all(), f"{name}: env {e} ({kind}): a step without a solver iteration"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
-    ap.add_argument("--out", default=HERE)
-    ap.add_argument("--lib", default=None, help="the library to record with (default: the product build)")
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
+def record(names, lib_path=None):
     held, differ = {}, {}
-    for name in CASES:
-        if a.cases and name not in a.cases:
-            continue
-        data, _ = run_case(name, lib_path=a.lib and os.path.abspath(a.lib))
+    for name in names:
+        data, _ = run_case(name, lib_path=lib_path)
         check_case(name, data)
         held[name], differ[name] = check_twin(name, data)
-        path = os.path.join(a.out, f"spill_diet_{name}.npz")
-        np.savez_compressed(path, **data)
-        kb = os.path.getsize(path) / 1024
-        assert kb < 100, f"{path}: {kb:.0f} KB"
-        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
-    if not a.cases:
+        yield name, data
+    if len(names) == len(CASES):
         check_all(held, differ, {len(kw["layout"]) for kw in CASES.values()})
 
 
 if __name__ == "__main__":
-    main()
+    F.main(sys.modules[__name__])

@@ -1,7 +1,7 @@
 """Record the HIP engine's bits on the step kernel's paths that the other fixtures leave dark (needs
 the GPU): tests/golden/step_paths_<case>.npz.
 
-    python tests/golden/make_step_paths.py [--out DIR] [case ...]
+    python tests/golden/make_step_paths.py [--out DIR] [--lib libzbot_hip.so] [case ...]
 
 engine_bits, smooth_bits and const_staging pin 64-env runs, n = 2 and 3, resets and ghost passes,
 the limit row in every env of a wave, and non-default solver fields. Three things stay open that a
@@ -22,25 +22,19 @@ rewrite of the solver loop's lane bookkeeping or of the step end can get wrong:
                 other output keeps its bits.
 
 Observation noise stays on and autoreset stays on, as in the headline configuration. main() refuses
-to write a case whose premise fails.
+to write a case whose premise fails. What the engine-bit families share is in tests/bit_fixtures.py.
 """
 
-import argparse
 import os
 import sys
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
-for p in (os.path.join(ROOT, "ksim-gym-zbot_amd"), os.path.dirname(HERE), HERE):
-    if p not in sys.path:
-        sys.path.insert(0, p)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # tests/, when run as a script
+import bit_fixtures as F  # noqa: E402
+from zbot_amd import default_config  # noqa: E402
 
-import make_engine_bits as G  # noqa: E402
-import make_smooth_bits as S  # noqa: E402
-
-DBG_MISC = 1728  # csrc/zb_internal.h ZB_DBG_MISC: nefc, ncon, ...
+FAMILY, MAX_KB = "step_paths", 100
 LIMIT_JOINT = ("left_elbow_roll", 1)  # env 0 of limit_one_cg: past the upper bound
 OUTPUT_MODES = (("full_", dict()), ("noextra_", dict(extras=False)), ("noterms_", dict(terms=False)))
 
@@ -52,75 +46,53 @@ CASES = {
 }
 
 
-def case_noise(steps, n, seed):
-    z = np.random.default_rng(seed).standard_normal((steps, n, 20))
-    return np.clip(np.rint(z * 32.0), -127, 127).astype(np.int8)
+def inputs(name):
+    kw = CASES[name]
+    return {"noise_q": F.action_noise(kw["seed"], kw["steps"], kw["n"])}
 
 
 def start_state(cm, kw, st):
     """The reset state rows `st`, env 0 moved past its joint limit for limit_one_cg."""
     st = st.copy()
     if kw.get("limit_one"):
-        joint, side = LIMIT_JOINT
-        b = S.hinge(cm, joint)
-        st[0, b.qposadr] = np.float32(b.jrange[1] + S.PAST if side > 0 else b.jrange[0] - S.PAST)
+        F.set_past(cm, st[0], *LIMIT_JOINT)
     return st
 
 
 def extra_rows(cm, dbg):
     """Per env: constraint rows beyond the contacts' four each and the friction-loss rows."""
     nfl = sum(1 for d in range(cm.nv) if float(cm.cmodel.dof_frictionloss[d]) > 0.0)
-    nefc = dbg[:, DBG_MISC + 0].astype(np.int64)
-    ncon = dbg[:, DBG_MISC + 1].astype(np.int64)
+    nefc = dbg[:, F.DBG_MISC + 0].astype(np.int64)
+    ncon = dbg[:, F.DBG_MISC + 1].astype(np.int64)
     return nefc - 4 * ncon - nfl, nefc, ncon
 
 
-def run_engine(cm, cfg, kw, actions, **step_kw):
+def run_mode(cm, cfg, kw, actions, lib_path=None, **step_kw):
     """One engine through the case's steps; the arrays a fixture keeps (every output buffer)."""
-    import torch  # noqa: PLC0415
-    from zbot_amd.engine import HipEngine  # noqa: PLC0415
-
-    n = kw["n"]
-    eng = HipEngine(cm, cfg, n, seed=kw["seed"])
-    eng.reset()
-    st = start_state(cm, kw, eng.get_state().cpu().numpy())
-    eng.set_state(torch.from_numpy(st))
+    r = F.Run(cm, cfg, kw["n"], kw["seed"], actions, start=lambda st: start_state(cm, kw, st), lib_path=lib_path,
+              step_kw=step_kw, final=("start_state", "final_state", "last"))
     # the buffers a switched-off output leaves alone start from zeros
     for k in ("obs_extra", "reward_terms"):
-        getattr(eng, k).zero_()
-    d = {"start_state": st}
+        getattr(r.eng, k).zero_()
+    d = {}
     if kw.get("limit_one"):
-        d["start_dbg_misc"] = eng.debug_forward(torch.from_numpy(st)).cpu().numpy()[:, DBG_MISC:DBG_MISC + 2].copy()
-        eng.set_state(torch.from_numpy(st))
-    rows = {"reward": [], "done": [], "success": [], "solver_iters": []}
-    out = None
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a[:n])).cuda(), **step_kw)
-        torch.cuda.synchronize()
-        for k in ("reward", "done", "success"):
-            rows[k].append(out[k].cpu().numpy().copy())
-        rows["solver_iters"].append(eng.solver_iters().cpu().numpy())
-    d.update({k: np.stack(v) for k, v in rows.items()})
-    d["final_state"] = eng.get_state().cpu().numpy()
-    for k, v in out.items():
-        d[f"last_{k}"] = v.cpu().numpy().copy()
+        st = r.torch.from_numpy(r.start_state)
+        d["start_dbg_misc"] = r.eng.debug_forward(st).cpu().numpy()[:, F.DBG_MISC:F.DBG_MISC + 2].copy()
+        r.eng.set_state(st)
+    d.update(r.run())
     return d
 
 
-def run_case(name, noise_q=None):
+def run_case(name, noise_q=None, lib_path=None):
     """The arrays of one case, keyed as in its fixture. `noise_q`: the fixture's own (a replay)."""
-    from zbot_amd import compile_model, default_config  # noqa: PLC0415
-
     kw = CASES[name]
-    cm = compile_model()
+    cm = F.model()
     cfg = default_config(solver=kw["solver"])
     if noise_q is None:
-        noise_q = case_noise(kw["steps"], kw["n"], kw["seed"])
-    actions = G.case_actions(cm, noise_q)
+        noise_q = inputs(name)["noise_q"]
     data = {"noise_q": noise_q}
     for tag, step_kw in (OUTPUT_MODES if kw.get("modes") else (("", dict()),)):
-        for k, v in run_engine(cm, cfg, kw, actions, **step_kw).items():
-            data[tag + k] = v
+        data.update(F.tagged(tag, run_mode(cm, cfg, kw, F.actions(cm, noise_q), lib_path, **step_kw)))
     return data, cm
 
 
@@ -129,13 +101,13 @@ def check_case(name, data, cm) -> None:
     kw = CASES[name]
     tags = [t for t, _ in OUTPUT_MODES] if kw.get("modes") else [""]
     for tag in tags:
-        assert np.isfinite(data[tag + "final_state"][:, :58]).all(), f"{name}: non-finite state"
+        assert np.isfinite(data[tag + "final_state"][:, F.motion_cols(cm)]).all(), f"{name}: non-finite state"
         assert (data[tag + "solver_iters"] > 0).all(), f"{name}: a step without a solver iteration"
     if kw["n"] == 1:
         assert data["done"].shape == (kw["steps"], 1) and not data["done"].any(), f"{name}: env 0 terminated"
     if kw.get("limit_one"):
-        dbg = np.zeros((kw["n"], DBG_MISC + 2), np.float32)
-        dbg[:, DBG_MISC:] = data["start_dbg_misc"]
+        dbg = np.zeros((kw["n"], F.DBG_MISC + 2), np.float32)
+        dbg[:, F.DBG_MISC:] = data["start_dbg_misc"]
         extra, nefc, ncon = extra_rows(cm, dbg)
         print(f"  {name}: nefc {nefc.tolist()} ncon {ncon.tolist()} rows beyond contacts and friction loss {extra.tolist()}")
         assert extra.tolist() == [1, 0], f"{name}: limit rows per env {extra.tolist()}, wanted [1, 0]"
@@ -151,23 +123,5 @@ def check_case(name, data, cm) -> None:
                 assert np.array_equal(data[tag + k], data["full_" + k], equal_nan=True), f"{name}: {tag}{k} moved"
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("cases", nargs="*", help="case names to (re)generate; default: all")
-    ap.add_argument("--out", default=HERE)
-    a = ap.parse_args()
-    os.makedirs(a.out, exist_ok=True)
-    for name in CASES:
-        if a.cases and name not in a.cases:
-            continue
-        data, cm = run_case(name)
-        check_case(name, data, cm)
-        path = os.path.join(a.out, f"step_paths_{name}.npz")
-        np.savez_compressed(path, **data)
-        kb = os.path.getsize(path) / 1024
-        assert kb < 100, f"{path}: {kb:.0f} KB"
-        print(f"{name}: {len(data)} arrays, {kb:.0f} KB")
-
-
 if __name__ == "__main__":
-    main()
+    F.main(sys.modules[__name__])

@@ -15,72 +15,48 @@ with, moves bits here (array_equal):
 """
 
 import gc
-import os
-import sys
 
-import numpy as np
+import bit_fixtures as F
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_const_records as G  # noqa: E402
+import make_const_records as G  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def load(name):
-    return np.load(os.path.join(HERE, "golden", f"const_records_{name}.npz"))
 
 
 @pytest.mark.parametrize("solver", G.SOLVERS)
 @pytest.mark.parametrize("case", list(G.CASES))
 def test_model_case(torch_gpu, case, solver):
-    want = load(case)
+    want = F.load(G.FAMILY, case)
     ncon = G.contact_counts(case, want["qpos"])
     assert min(ncon) >= 1, f"{case}: an env starts without a contact row ({ncon})"
     got = G.run_case(case, solver, want["noise_q"], want["qpos"])
     assert sorted(got) == sorted(k for k in want.files if k.startswith(solver + "_"))
-    bad = [k for k in got if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{case} {solver}: arrays that differ from the recorded bits: {bad}"
 
 
-def handle_run(want, h):
-    return G.Run(h, "cg", G.NMAX, want["noise_q"], want[f"qpos_{h}"])
-
-
-def differing(got, want, prefix):
-    return [k for k in G.KEYS if not np.array_equal(got[k], want[f"{prefix}_{k}"], equal_nan=True)]
-
-
 def test_two_models_interleaved(torch_gpu):
-    want = load("handles")
-    ra, rb = handle_run(want, "default"), handle_run(want, "limbs")
+    want = F.load(G.FAMILY, "handles")
+    ra, rb = G.handle_alone("default", want), G.handle_alone("limbs", want)
     for _ in range(G.STEPS):
         ra.step()
         rb.step()
     for h, r in (("default", ra), ("limbs", rb)):
-        bad = differing(r.result(), want, h)
+        bad = F.differing(r.result(), want, G.KEYS, h + "_")
         assert not bad, f"handle {h} beside the other model's: differs from its run alone in {bad}"
 
 
 @pytest.mark.parametrize("first,second", [("default", "limbs"), ("limbs", "default")])
 def test_handle_created_after_another_model_was_destroyed(torch_gpu, first, second):
-    want = load("handles")
-    a = handle_run(want, first)
+    want = F.load(G.FAMILY, "handles")
+    a = G.handle_alone(first, want)
     a.step()
     del a
     gc.collect()  # HipEngine.__del__: zb_destroy
-    b = handle_run(want, second)
+    b = G.handle_alone(second, want)
     for _ in range(G.STEPS):
         b.step()
-    bad = differing(b.result(), want, second)
+    bad = F.differing(b.result(), want, G.KEYS, second + "_")
     assert not bad, f"the {second} handle created after the {first} one differs from its recorded bits in {bad}"

@@ -15,70 +15,45 @@ bit for bit (array_equal):
 """
 
 import gc
-import os
-import sys
 
-import numpy as np
+import bit_fixtures as F
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_const_staging as G  # noqa: E402
+import make_const_staging as G  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
-def load(name):
-    return np.load(os.path.join(HERE, "golden", f"const_staging_{name}.npz"))
-
-
-def differing(got, want, prefix):
-    return [k for k in G.KEYS if not np.array_equal(got[k], want[f"{prefix}_{k}"], equal_nan=True)]
-
-
 @pytest.mark.parametrize("solver", G.SOLVERS)
 def test_non_default_solver_fields(torch_gpu, solver):
-    want = load(solver)
+    want = F.load(G.FAMILY, solver)
     got = G.run_solver_cases(solver, want["noise_q"], want["qpos"])
     assert sorted(got) == sorted(k for k in want.files if k not in ("noise_q", "qpos"))
-    bad = [k for k in got if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{solver}: arrays that differ from the recorded bits: {bad}"
-
-
-def handle_run(want, h):
-    cfg_name, model_name = G.HANDLES[h]
-    return G.Run(cfg_name, "cg", model_name, G.NMAX, want["noise_q"], want["qpos_limbs" if model_name else "qpos"])
 
 
 @pytest.mark.parametrize("a,b", [("default", "it3"), ("default", "limbs")])
 def test_two_handles_interleaved(torch_gpu, a, b):
-    want = load("handles")
-    ra, rb = handle_run(want, a), handle_run(want, b)
+    want = F.load(G.FAMILY, "handles")
+    ra, rb = G.handle_alone(a, want), G.handle_alone(b, want)
     for _ in range(G.STEPS):
         ra.step()
         rb.step()
     for h, r in ((a, ra), (b, rb)):
-        bad = differing(r.result(), want, h)
+        bad = F.differing(r.result(), want, G.KEYS, h + "_")
         assert not bad, f"handle {h} beside {b if h == a else a}: differs from its run alone in {bad}"
 
 
 def test_handle_created_after_another_was_destroyed(torch_gpu):
-    want = load("handles")
-    first = handle_run(want, "default")
+    want = F.load(G.FAMILY, "handles")
+    first = G.handle_alone("default", want)
     first.step()
     del first
     gc.collect()  # HipEngine.__del__: zb_destroy
-    second = handle_run(want, "it3_limbs")
+    second = G.handle_alone("it3_limbs", want)
     for _ in range(G.STEPS):
         second.step()
-    bad = differing(second.result(), want, "it3_limbs")
+    bad = F.differing(second.result(), want, G.KEYS, "it3_limbs_")
     assert not bad, f"the second handle differs from its recorded bits in {bad}"

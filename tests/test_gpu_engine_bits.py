@@ -15,32 +15,19 @@ the GPU, after the oracle-based tests have passed, and commits them with the cha
     python tests/golden/make_engine_bits.py
 """
 
-import os
-import sys
-
-import numpy as np
+import bit_fixtures as F
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_engine_bits as G  # noqa: E402
+import make_engine_bits as G  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
 @pytest.mark.parametrize("name", list(G.CASES))
 def test_engine_reproduces_recorded_bits(torch_gpu, name):
-    want = np.load(os.path.join(HERE, "golden", f"engine_bits_{name}.npz"))
+    want = F.load(G.FAMILY, name)
     got, *_ = G.run_case(name, noise_q=want["noise_q"])
     assert sorted(got) == sorted(want.files)
-    bad = [k for k in want.files if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{name}: arrays that differ from the recorded bits: {bad}"

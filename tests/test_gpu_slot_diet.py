@@ -17,45 +17,26 @@ The fixtures were recorded with the library of commit 132bf6a, the parent of the
 CG wave's non-VALU issue slots. A change meant to keep every rounding passes unchanged.
 """
 
-import os
-import sys
-
-import numpy as np
+import bit_fixtures as F
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_slot_diet as D  # noqa: E402
-
-
-def _fixture(name):
-    return np.load(os.path.join(HERE, "golden", f"slot_diet_{name}.npz"))
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
+import make_slot_diet as D  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 
 @pytest.mark.parametrize("name", list(D.CASES))
 def test_fixture_holds_every_zone(name):
     """On the CPU twin: the recorded start states and actions put every zone into one wave."""
-    from zbot_amd import compile_model
-
-    want = _fixture(name)
-    D.check_zones(name, compile_model(), {k: want[k] for k in ("start_state", "start_rand", "noise_q")})
+    want = F.load(D.FAMILY, name)
+    D.check_zones(name, F.model(), {k: want[k] for k in ("start_state", "start_rand", "noise_q")})
 
 
 def _replay(name, swap):
-    want = _fixture(name)
+    want = F.load(D.FAMILY, name)
     got, cm = D.run_case(name, noise_q=want["noise_q"], swap=swap)
     D.check_case(name, got, cm, zones=False)
     assert sorted(got) == sorted(want.files)
-    bad = [k for k in want.files if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{name} (swapped: {swap}): arrays that differ from the recorded bits: {bad}"
 
 

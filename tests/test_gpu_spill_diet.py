@@ -18,28 +18,11 @@ The fixtures were recorded with the library of commit 57ba670, the parent of the
 search's exit path. A change meant to keep every rounding passes unchanged.
 """
 
-import os
-import sys
-
-import numpy as np
+import bit_fixtures as F
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_spill_diet as P  # noqa: E402
-
-
-def _fixture(name):
-    return np.load(os.path.join(HERE, "golden", f"spill_diet_{name}.npz"))
-
-
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
+import make_spill_diet as P  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 
 @pytest.fixture(scope="module")
@@ -47,7 +30,7 @@ def twins():
     """check_twin of every fixture, once: {case: (counts held, a wave with differing exits)}."""
     out = {}
     for name in P.CASES:
-        want = _fixture(name)
+        want = F.load(P.FAMILY, name)
         out[name] = P.check_twin(name, {k: want[k] for k in ("start_state", "start_rand", "noise_q")})
     return out
 
@@ -56,7 +39,7 @@ def twins():
 def test_fixture_holds_its_case(twins, name):
     """On the CPU twin: the recorded start states and actions take the case's paths (check_twin
     asserts them), and the recorded flags agree."""
-    want = _fixture(name)
+    want = F.load(P.FAMILY, name)
     P.check_case(name, {k: want[k] for k in ("states", "done", "solver_iters")})
     assert name in twins
 
@@ -64,15 +47,15 @@ def test_fixture_holds_its_case(twins, name):
 def test_fixtures_hold_every_exit(twins):
     """Together: 0, 1, 2, 3 to 7 and 8 evaluations, differing exits in one wave, n = 1 and n = 3."""
     P.check_all({k: v[0] for k, v in twins.items()}, {k: v[1] for k, v in twins.items()},
-                {_fixture(name)["start_state"].shape[0] for name in P.CASES})
+                {F.load(P.FAMILY, name)["start_state"].shape[0] for name in P.CASES})
 
 
 def _replay(name, swap):
-    want = _fixture(name)
+    want = F.load(P.FAMILY, name)
     got, _ = P.run_case(name, noise_q=want["noise_q"], swap=swap)
     P.check_case(name, got)
     assert sorted(got) == sorted(want.files)
-    bad = [k for k in want.files if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{name} (swapped: {swap}): arrays that differ from the recorded bits: {bad}"
 
 

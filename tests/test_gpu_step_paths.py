@@ -21,80 +21,46 @@ treats the upper team differently. A and B differ where the solver's copies diff
 hinge past its range (a joint-limit row), A has none.
 """
 
-import os
-import sys
-
+import bit_fixtures as F
 import numpy as np
 import pytest
+from bit_fixtures import torch_gpu  # noqa: F401
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import make_step_paths as P  # noqa: E402
+import make_step_paths as P  # isort: skip  (tests/golden: on the path once bit_fixtures is imported)
 
 pytestmark = pytest.mark.gpu
 
 SYM_STEPS = 3
 
 
-@pytest.fixture(scope="module")
-def torch_gpu():
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU")
-    return torch
-
-
 @pytest.mark.parametrize("name", list(P.CASES))
 def test_engine_reproduces_step_paths(torch_gpu, name):
-    want = np.load(os.path.join(HERE, "golden", f"step_paths_{name}.npz"))
+    want = F.load(P.FAMILY, name)
     got, cm = P.run_case(name, noise_q=want["noise_q"])
     P.check_case(name, got, cm)
     assert sorted(got) == sorted(want.files)
-    bad = [k for k in want.files if not np.array_equal(got[k], want[k], equal_nan=True)]
+    bad = F.differing(got, want)
     assert not bad, f"{name}: arrays that differ from the recorded bits: {bad}"
-
-
-def _run_pair(torch, cm, cfg, st, rnd, actions):
-    from zbot_amd.engine import HipEngine
-
-    eng = HipEngine(cm, cfg, 2, seed=51)
-    eng.reset()
-    eng.set_state(torch.from_numpy(st))
-    eng.set_rand(torch.from_numpy(rnd))
-    rows = []
-    for a in actions:
-        out = eng.step(torch.from_numpy(np.ascontiguousarray(a)).cuda())
-        torch.cuda.synchronize()
-        d = {k: v.cpu().numpy().copy() for k, v in out.items()}
-        d["solver_iters"] = eng.solver_iters().cpu().numpy()
-        d["state"] = eng.get_state().cpu().numpy()
-        rows.append(d)
-    return rows
 
 
 @pytest.mark.parametrize("solver", ["cg", "newton"])
 def test_teams_are_symmetric(torch_gpu, solver):
-    torch = torch_gpu
-    from zbot_amd import compile_model, default_config
-    from zbot_amd.engine import HipEngine
+    from zbot_amd import default_config
 
-    cm = compile_model()
+    cm = F.model()
     cfg = default_config(solver=solver, obs_noise=False, autoreset=False)
-    eng = HipEngine(cm, cfg, 2, seed=51)
-    eng.reset()
-    st = eng.get_state().cpu().numpy()
-    rnd = eng.get_rand().cpu().numpy()
-    del eng
-    # B: the reset state of env 1 with one limited hinge past its upper bound; A: env 0's reset state
-    b = P.S.hinge(cm, P.LIMIT_JOINT[0])
-    st[1, b.qposadr] = np.float32(b.jrange[1] + P.S.PAST)
-    assert not np.array_equal(st[0, :58], st[1, :58])
-    actions = P.G.case_actions(cm, P.case_noise(SYM_STEPS, 2, 52))
-    ab = _run_pair(torch, cm, cfg, st, rnd, actions)
-    ba = _run_pair(torch, cm, cfg, st[::-1].copy(), rnd[::-1].copy(), actions[:, ::-1])
+
+    def start(st):
+        # B: the reset state of env 1 with one limited hinge past its upper bound; A: env 0's reset state
+        F.set_past(cm, st[1], *P.LIMIT_JOINT)
+        assert not np.array_equal(st[0, F.motion_cols(cm)], st[1, F.motion_cols(cm)])
+        return st
+
+    # every output, solver_iters and the state of every step, of [A, B] and of [B, A] with its rows swapped back
+    ab, ba = (F.run(cm, cfg, 2, 51, F.actions(cm, F.action_noise(52, SYM_STEPS, 2)), start=start, rand="own",
+                    swap=swap, per_step=None) for swap in (False, True))
     for t in range(SYM_STEPS):
-        assert not ab[t]["done"].any(), "an env terminated: the reset draws depend on the env index"
-        assert (ab[t]["solver_iters"] > 0).all()
-        bad = [k for k in ab[t] if not np.array_equal(ab[t][k], ba[t][k][::-1], equal_nan=True)]
+        assert not ab["done"][t].any(), "an env terminated: the reset draws depend on the env index"
+        assert (ab["solver_iters"][t] > 0).all()
+        bad = [k for k in ab if not np.array_equal(ab[k][t], ba[k][t], equal_nan=True)]
         assert not bad, f"{solver} step {t}: outputs that are not the swapped rows: {bad}"
