@@ -243,6 +243,73 @@ int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, i
 int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
                              uint64_t seed, uint32_t epoch);
 
+/*
+ * ---- Rollout summary: every sum a rollout's telemetry needs, in one fixed-order reduction ----
+ * Added in ABI version 5 (zb_rollout_summary_partials_words, zb_rollout_summary,
+ * zb_rollout_summary_host).
+ *
+ * One pass over the T*n rows of a finished rollout, in (t, env) order, into ZB_SUMMARY_WORDS fp64
+ * words (zbot_amd.metrics.rollout_telemetry turns them into means, rates and the explained
+ * variance):
+ *
+ *   ZB_SUM_TERMS + i        sum of reward term i (i < 12, include/zbot.h ZB_T_*)
+ *   ZB_SUM_CMD_TERMS + i    sum of command term i (i < 5, include/zbot_command.h)
+ *   ZB_SUM_REWARD, _SQ      sum of reward, of reward^2
+ *   ZB_SUM_DONE, _SUCCESS   number of rows with done != 0, with success != 0
+ *   ZB_SUM_LOG_PROB         sum over rows of the row's log-prob: its 20 joints, the first converted
+ *                           to fp64 and the others added to it in joint order in fp64
+ *   ZB_SUM_VALUE, _SQ       sum of value, of value^2
+ *   ZB_SUM_TARGET, _SQ      sum of value target, of target^2
+ *   ZB_SUM_RESIDUAL_SQ      sum of (target - value)^2
+ *   ZB_SUM_ROWS             the row count T*n (a leaf of 1.0 per row)
+ *   28 .. 31                +0.0
+ *
+ * A leaf is formed in fp64 from the fp32 (or uint8) inputs: squares and the difference are taken
+ * after the conversion. The words of a null plane are +0.0. Every word is reduced over the rows by
+ * the "Reduction tree" above (balanced pairwise tree, zero-padded to a power of two, adjacent pairs
+ * first, fp64, root + 0.0; no floating-point atomics): a workgroup reduces ZB_LOSS_ROWS_PER_BLOCK
+ * rows for all words at once into one partial of ZB_SUMMARY_WORDS words, and a second,
+ * single-workgroup launch runs the tree over the partials.
+ *
+ *   reward_terms   [T, n, 12] fp32 (nullable)     command_terms [T, n, 5] fp32 (nullable)
+ *   reward         [T, n] fp32                    done [T, n] uint8; success [T, n] uint8 (nullable)
+ *   log_prob       [T, n, 20] fp32 (nullable)
+ *   values, value_targets  [T, n] fp32 (nullable, both or neither)
+ *   partials       [zb_rollout_summary_partials_words(T, n)] fp64 scratch
+ *   sums_out       [ZB_SUMMARY_WORDS] fp64
+ * T >= 1, n >= 1, T*n <= 2^28. A workgroup's share of a plane is contiguous and starts on a multiple
+ * of 16 bytes from the plane's start, so each plane whose pointer is 16-byte aligned is read in
+ * 16-byte accesses (whatever its row size: 48, 20, 80, 4 bytes or 1), the others in 4-byte ones
+ * (single bytes for the uint8 planes). Device pointers; asynchronous on `stream`, nothing
+ * allocated, nothing synchronized; bad arguments return ZB_EARG and launch nothing. The host twin
+ * takes host pointers, forms the same leaves and runs the same tree: the kernel's bit reference.
+ */
+#define ZB_SUMMARY_WORDS 32
+#define ZB_SUM_TERMS 0
+#define ZB_SUM_CMD_TERMS 12
+#define ZB_SUM_REWARD 17
+#define ZB_SUM_REWARD_SQ 18
+#define ZB_SUM_DONE 19
+#define ZB_SUM_SUCCESS 20
+#define ZB_SUM_LOG_PROB 21
+#define ZB_SUM_VALUE 22
+#define ZB_SUM_VALUE_SQ 23
+#define ZB_SUM_TARGET 24
+#define ZB_SUM_TARGET_SQ 25
+#define ZB_SUM_RESIDUAL_SQ 26
+#define ZB_SUM_ROWS 27
+#define ZB_SUM_USED 28 /* words below this index carry a sum */
+
+/* fp64 words of the `partials` scratch zb_rollout_summary needs for a [T, n] rollout (0: bad size). */
+size_t zb_rollout_summary_partials_words(int T, int n);
+
+int zb_rollout_summary(const float* reward_terms, const float* command_terms, const float* reward,
+                       const uint8_t* done, const uint8_t* success, const float* log_prob, const float* values,
+                       const float* value_targets, int T, int n, double* partials, double* sums_out, void* stream);
+int zb_rollout_summary_host(const float* reward_terms, const float* command_terms, const float* reward,
+                            const uint8_t* done, const uint8_t* success, const float* log_prob, const float* values,
+                            const float* value_targets, int T, int n, double* sums_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,6 @@
 CXX ?= g++
 SAN = -fsanitize=address,undefined -fsanitize=bounds -fno-sanitize-recover=all -fno-omit-frame-pointer
 OBJDIR ?= build
-$(OBJDIR)/zb_host_selftest: zb_host.cpp zb_host.h zb_host_selftest.cpp ../../include/zbot.h ../../include/zbot_model.h ../../include/zbot_layout.h ../../include/zbot_command.h
+$(OBJDIR)/zb_host_selftest: zb_host.cpp zb_host.h zb_host_selftest.cpp ../../include/zbot.h ../../include/zbot_model.h ../../include/zbot_layout.h ../../include/zbot_command.h ../../include/zbot_ppo.h
 	@mkdir -p $(OBJDIR)
 	$(CXX) -std=c++17 -O1 -g $(SAN) -Wall -I../../include -o $@ zb_host.cpp zb_host_selftest.cpp

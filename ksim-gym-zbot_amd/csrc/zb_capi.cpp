@@ -23,7 +23,7 @@ using zb::check_cfg;
 using zb::check_model;
 using zb::fail;
 
-#define ZB_ABI_VERSION 4
+#define ZB_ABI_VERSION 5
 
 struct ZbHandle {
   int device;
@@ -520,6 +520,38 @@ int zb_ppo_loss(const float* log_prob, const float* old_log_prob, const float* a
   a.vec = 0;
   hipError_t e = zb::launch_ppo_loss(a, sums_out, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_ppo_loss launch: %s", hipGetErrorString(e));
+  return ZB_OK;
+}
+
+/* ---- rollout summary (include/zbot_ppo.h "Rollout summary") ---- */
+
+size_t zb_rollout_summary_partials_words(int T, int n) {
+  if (T < 1 || n < 1) return 0;
+  const size_t rows = (size_t)T * (size_t)n;
+  if (rows > ((size_t)1 << 28)) return 0;
+  return ZB_SUMMARY_WORDS * ((rows + ZB_LOSS_ROWS_PER_BLOCK - 1) / ZB_LOSS_ROWS_PER_BLOCK);
+}
+
+int zb_rollout_summary(const float* reward_terms, const float* command_terms, const float* reward,
+                       const uint8_t* done, const uint8_t* success, const float* log_prob, const float* values,
+                       const float* value_targets, int T, int n, double* partials, double* sums_out, void* stream) {
+  if (int rc = zb::check_summary_args("zb_rollout_summary", reward, done, values, value_targets, T, n, partials, 1,
+                                      sums_out))
+    return rc;
+  zb::SummaryArgs a;
+  a.terms = reward_terms;
+  a.cmd = command_terms;
+  a.reward = reward;
+  a.done = done;
+  a.success = success;
+  a.log_prob = log_prob;
+  a.values = values;
+  a.targets = value_targets;
+  a.rows = (size_t)T * (size_t)n;
+  a.partials = partials;
+  a.vec = 0;
+  hipError_t e = zb::launch_rollout_summary(a, sums_out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_rollout_summary launch: %s", hipGetErrorString(e));
   return ZB_OK;
 }
 

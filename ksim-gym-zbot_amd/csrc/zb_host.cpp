@@ -6,7 +6,8 @@
  * the minibatch twins ("Minibatches": zb_minibatch_perm_host, zb_minibatch_gather_host), that of
  * csrc/zb_minibatch.hip; and the velocity commands' twins (include/zbot_command.h:
  * zb_command_initial_host, zb_command_next_host, zb_command_rewards_host), built on the header the
- * step kernel includes.
+ * step kernel includes; and the rollout summary's twin ("Rollout summary":
+ * zb_rollout_summary_host), the bit reference of zb_ppo.hip's summary kernels.
  * Plain C++ (no HIP): the product library links it, and csrc/sanitize.mk builds it with the host
  * sanitizers for tests/test_sanitizers.py.
  */
@@ -475,6 +476,23 @@ int check_gather_args(const char* what, const ZbGatherItem* items, int n_items, 
   return ZB_OK;
 }
 
+int check_summary_args(const char* what, const void* reward, const void* done, const void* values,
+                       const void* value_targets, int T, int n, const void* partials, int need_partials,
+                       const void* sums_out) {
+  if (T < 1) return fail(ZB_EARG, "%s: T = %d (at least 1)", what, T);
+  if (n < 1) return fail(ZB_EARG, "%s: n = %d (at least 1)", what, n);
+  if ((unsigned long long)T * (unsigned long long)n > (1ull << 28))
+    return fail(ZB_EARG, "%s: T * n = %d * %d rows (at most 2^28)", what, T, n);
+  if (!reward) return fail(ZB_EARG, "%s: null reward", what);
+  if (!done) return fail(ZB_EARG, "%s: null done", what);
+  if (!values != !value_targets)
+    return fail(ZB_EARG, "%s: %s without %s (both or neither)", what, values ? "values" : "value_targets",
+                values ? "value_targets" : "values");
+  if (need_partials && !partials) return fail(ZB_EARG, "%s: null partials", what);
+  if (!sums_out) return fail(ZB_EARG, "%s: null sums_out", what);
+  return ZB_OK;
+}
+
 float inv_total(double total) { return (float)(1.0 / total); }
 
 AdamCoef adam_coefficients(double beta1, double beta2, int step) {
@@ -562,6 +580,47 @@ int zb_grad_combine_host(const float* parts, int world, size_t count, float* gra
   for (size_t i = 0; i < count; i++)
     grad[i] = (float)zb::tree_root([&](size_t r) { return (double)parts[r * count + i]; }, (size_t)world);
   sq_out[0] = zb::tree_root([&](size_t i) { const double g = (double)grad[i]; return g * g; }, count);
+  return ZB_OK;
+}
+
+int zb_rollout_summary_host(const float* reward_terms, const float* command_terms, const float* reward,
+                            const uint8_t* done, const uint8_t* success, const float* log_prob, const float* values,
+                            const float* value_targets, int T, int n, double* sums_out) {
+  if (int rc = zb::check_summary_args("zb_rollout_summary_host", reward, done, values, value_targets, T, n, nullptr, 0,
+                                      sums_out))
+    return rc;
+  const size_t rows = (size_t)T * (size_t)n;
+  for (int w = 0; w < ZB_SUMMARY_WORDS; w++) sums_out[w] = 0.0;
+  if (reward_terms)
+    for (int k = 0; k < 12; k++)
+      sums_out[ZB_SUM_TERMS + k] = zb::tree_root([&](size_t i) { return (double)reward_terms[i * 12 + k]; }, rows);
+  if (command_terms)
+    for (int k = 0; k < ZB_NUM_CMD_TERMS; k++)
+      sums_out[ZB_SUM_CMD_TERMS + k] =
+          zb::tree_root([&](size_t i) { return (double)command_terms[i * ZB_NUM_CMD_TERMS + k]; }, rows);
+  sums_out[ZB_SUM_REWARD] = zb::tree_root([&](size_t i) { return (double)reward[i]; }, rows);
+  sums_out[ZB_SUM_REWARD_SQ] = zb::tree_root([&](size_t i) { const double r = (double)reward[i]; return r * r; }, rows);
+  sums_out[ZB_SUM_DONE] = zb::tree_root([&](size_t i) { return done[i] ? 1.0 : 0.0; }, rows);
+  if (success) sums_out[ZB_SUM_SUCCESS] = zb::tree_root([&](size_t i) { return success[i] ? 1.0 : 0.0; }, rows);
+  if (log_prob)
+    sums_out[ZB_SUM_LOG_PROB] = zb::tree_root(
+        [&](size_t i) {
+          const float* p = log_prob + i * ZBL_JOINTS;
+          double s = (double)p[0];
+          for (int j = 1; j < ZBL_JOINTS; j++) s = s + (double)p[j];
+          return s;
+        },
+        rows);
+  if (values) {
+    sums_out[ZB_SUM_VALUE] = zb::tree_root([&](size_t i) { return (double)values[i]; }, rows);
+    sums_out[ZB_SUM_VALUE_SQ] = zb::tree_root([&](size_t i) { const double v = (double)values[i]; return v * v; }, rows);
+    sums_out[ZB_SUM_TARGET] = zb::tree_root([&](size_t i) { return (double)value_targets[i]; }, rows);
+    sums_out[ZB_SUM_TARGET_SQ] =
+        zb::tree_root([&](size_t i) { const double g = (double)value_targets[i]; return g * g; }, rows);
+    sums_out[ZB_SUM_RESIDUAL_SQ] = zb::tree_root(
+        [&](size_t i) { const double d = (double)value_targets[i] - (double)values[i]; return d * d; }, rows);
+  }
+  sums_out[ZB_SUM_ROWS] = zb::tree_root([](size_t) { return 1.0; }, rows);
   return ZB_OK;
 }
 

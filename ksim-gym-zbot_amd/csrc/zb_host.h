@@ -86,6 +86,11 @@ int combine_width(const float* parts, int world, size_t count, const float* grad
 int check_adamw_args(const char* what, const void* param, const void* grad, const void* m, const void* v,
                      size_t count, size_t frozen_tail, const void* sqnorms, int k, float max_grad_norm, float lr,
                      double beta1, double beta2, float eps, float weight_decay, int step);
+/* zb_rollout_summary / _host (include/zbot_ppo.h "Rollout summary"); `partials` is checked when
+   need_partials (the device entry point) */
+int check_summary_args(const char* what, const void* reward, const void* done, const void* values,
+                       const void* value_targets, int T, int n, const void* partials, int need_partials,
+                       const void* sums_out);
 /* the scalars both sides derive on the host, here only (zb_capi.cpp is built with relaxed flags):
    (float)(1 / total); AdamW's (float)beta, (float)(1 - beta), (float)(1 - beta^step), in fp64 */
 float inv_total(double total);

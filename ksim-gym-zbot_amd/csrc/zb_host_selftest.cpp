@@ -14,7 +14,10 @@
  * (include/zbot_command.h) get the same treatment: a joystick ZbCommandConfig with one word
  * corrupted goes to zb_command_config_check, and every copy that passes runs
  * zb_command_initial_host / _next_host / _rewards_host over a small batch whose outputs must then
- * lie where the law puts them. Prints one summary line.
+ * lie where the law puts them. Last, zb_rollout_summary_host (include/zbot_ppo.h) reads planes
+ * allocated to the byte at sizes around its tree's powers of two, with every subset of the nullable
+ * planes, so a read past a plane's end is an ASan report; its counts must be the exact integers
+ * and its bad arguments refused. Prints one summary line.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,6 +26,7 @@
 #include <vector>
 
 #include "zb_host.h"
+#include "zbot_ppo.h"
 
 static bool read_file(const char* path, void* dst, size_t bytes) {
   FILE* f = fopen(path, "rb");
@@ -161,8 +165,57 @@ int main(int argc, char** argv) {
       }
     }
   }
+  /* the rollout summary's twin */
+  const int shapes[][2] = {{1, 1}, {3, 85}, {4, 64}, {1, 257}, {7, 33}, {3, 259}};
+  long summaries = 0;
+  for (const auto& sh : shapes) {
+    const int T = sh[0], n = sh[1];
+    const size_t rows = (size_t)T * (size_t)n;
+    for (int mask = 0; mask < 32; mask++) {
+      auto plane = [&](size_t width) {
+        std::vector<float> v(rows * width);
+        for (float& x : v) x = (float)((double)(next_u64() >> 11) / 9007199254740992.0 * 2.0 - 1.0);
+        return v;
+      };
+      const std::vector<float> terms = plane(12), cterms = plane(ZB_NUM_CMD_TERMS), rew = plane(1), lp = plane(20),
+                               val = plane(1), tgt = plane(1);
+      std::vector<uint8_t> done(rows), succ(rows);
+      double ndone = 0.0, nsucc = 0.0;
+      for (size_t i = 0; i < rows; i++) {
+        done[i] = (uint8_t)(next_u64() % 4 == 0 ? 1 + next_u64() % 255 : 0);
+        succ[i] = (uint8_t)(done[i] && (next_u64() & 1));
+        ndone += done[i] ? 1.0 : 0.0;
+        nsucc += succ[i] ? 1.0 : 0.0;
+      }
+      double sums[ZB_SUMMARY_WORDS];
+      if (zb_rollout_summary_host(mask & 1 ? terms.data() : nullptr, mask & 2 ? cterms.data() : nullptr, rew.data(),
+                                  done.data(), mask & 4 ? succ.data() : nullptr, mask & 8 ? lp.data() : nullptr,
+                                  mask & 16 ? val.data() : nullptr, mask & 16 ? tgt.data() : nullptr, T, n,
+                                  sums) != ZB_OK) {
+        fprintf(stderr, "zb_rollout_summary_host refused %d x %d, planes 0x%x: %s\n", T, n, mask, zb_last_error());
+        return 1;
+      }
+      if (sums[ZB_SUM_ROWS] != (double)rows || sums[ZB_SUM_DONE] != ndone ||
+          sums[ZB_SUM_SUCCESS] != (mask & 4 ? nsucc : 0.0) || sums[ZB_SUM_USED] != 0.0 ||
+          (!(mask & 16) && sums[ZB_SUM_RESIDUAL_SQ] != 0.0)) {
+        fprintf(stderr, "zb_rollout_summary_host %d x %d, planes 0x%x: wrong counts\n", T, n, mask);
+        return 1;
+      }
+      if (zb_rollout_summary_host(nullptr, nullptr, rew.data(), done.data(), nullptr, nullptr, val.data(), nullptr, T, n,
+                                  sums) != ZB_EARG ||
+          zb_rollout_summary_host(nullptr, nullptr, rew.data(), nullptr, nullptr, nullptr, nullptr, nullptr, T, n,
+                                  sums) != ZB_EARG ||
+          zb_rollout_summary_host(nullptr, nullptr, rew.data(), done.data(), nullptr, nullptr, nullptr, nullptr, 0, n,
+                                  sums) != ZB_EARG) {
+        fprintf(stderr, "zb_rollout_summary_host accepted a bad argument\n");
+        return 1;
+      }
+      summaries++;
+    }
+  }
   printf("zb_host_selftest ok: %ld mutations, %ld accepted, %ld rejected, words %zu; command configs %ld accepted, "
-         "%ld rejected\n", mutations, accepted, rejected, words, cmd_accepted, cmd_rejected);
+         "%ld rejected; %ld rollout summaries\n", mutations, accepted, rejected, words, cmd_accepted, cmd_rejected,
+         summaries);
   delete m;
   delete model;
   return 0;

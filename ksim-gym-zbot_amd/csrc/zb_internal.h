@@ -287,6 +287,22 @@ hipError_t launch_grad_combine(const float* parts, int world, size_t count, floa
                                double* sq_out, bool vec, hipStream_t s);
 hipError_t launch_adamw(AdamArgs a, hipStream_t s);
 
+/* the rollout summary (zb_ppo.hip, include/zbot_ppo.h "Rollout summary") */
+struct SummaryArgs {
+  const float* terms;          /* [rows][12] or null */
+  const float* cmd;            /* [rows][5] or null */
+  const float* reward;         /* [rows] */
+  const uint8_t* done;         /* [rows] */
+  const uint8_t* success;      /* [rows] or null */
+  const float* log_prob;       /* [rows][20] or null */
+  const float* values;         /* [rows] or null */
+  const float* targets;        /* [rows] or null, with values */
+  size_t rows;                 /* T n */
+  double* partials;            /* [ceil(rows / ZB_LOSS_ROWS_PER_BLOCK)][ZB_SUMMARY_WORDS] */
+  int vec;                     /* set by the launcher: bit p = plane p (in the order above) is 16-byte aligned */
+};
+hipError_t launch_rollout_summary(SummaryArgs a, double* sums_out, hipStream_t s);
+
 /* the minibatch kernels (zb_minibatch.hip, include/zbot_ppo.h "Minibatches") */
 struct GatherArgs {
   GatherItemDev it[ZB_GATHER_MAX_ITEMS]; /* zb_host.h: the checked items with their access width */

@@ -32,6 +32,10 @@
  *                power of two keeps every level a perfect binary tree, so
  *                rank-order combining reproduces the one-GPU bits.
  *   normalize    grid-stride float4 stream, IEEE division.
+ *
+ * Also here: zb_rollout_summary, the fused fixed-order reduction of a finished rollout to 32 fp64
+ * sums (include/zbot_ppo.h "Rollout summary"; summary_kernel / summary_finish_kernel below),
+ * bit-identical to zb_rollout_summary_host in zb_host.cpp.
  */
 #include <hip/hip_runtime.h>
 
@@ -326,6 +330,230 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* gae, float*
   }
   for (long long i = n4 * 4 + (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride)
     adv[i] = (gae[i] - mean_f) / denom;
+}
+
+/* ---- zb_rollout_summary (include/zbot_ppo.h "Rollout summary") ----
+ *
+ *   summary_kernel  one workgroup = SROWS = 256 consecutive rows, a thread per row. The workgroup's
+ *                   share of every plane is one contiguous run that starts 256 rows into the plane,
+ *                   a multiple of 16 bytes whatever the row size, so it streams into LDS in 16-byte
+ *                   loads when the plane's pointer is aligned (a last, ragged workgroup ends in
+ *                   4-byte ones), else in 4-byte ones (bytes for the uint8 planes). LDS row strides
+ *                   are odd (13, 5, 21 words), so the thread of a row then reads conflict-free. It
+ *                   forms the row's 28 fp64 leaves; the tree over the 64 rows of a wave is six
+ *                   rounds of lane shuffles (1, 2, 4 .. 32 apart: adjacent pairs first), the tree
+ *                   over the four waves goes through LDS; partials[block][32].
+ *   summary_finish  one workgroup of 16 waves. A wave takes 64 consecutive partials, a lane one, all
+ *                   28 words in registers, and runs the same six rounds; the 16 wave roots of a
+ *                   pass of 1024 partials are combined in LDS. The roots of successive passes go
+ *                   through a binary counter, one slot per level and word, the carry chain of
+ *                   pairwise summation: together the balanced tree over the partials. Absent
+ *                   right halves are skipped: they are +0.0, adding them is exact, and the root is
+ *                   added to +0.0.
+ */
+constexpr int SROWS = ZB_LOSS_ROWS_PER_BLOCK; /* rows per workgroup = threads (a power of two) */
+constexpr int SW = ZB_SUMMARY_WORDS;
+constexpr int SU = ZB_SUM_USED;               /* words that carry a sum */
+constexpr int S_TERMS = 12, S_CMD = 5, S_LP = 20;
+constexpr int S_TERMS_LD = 13, S_CMD_LD = 5, S_LP_LD = 21;
+constexpr int FIN_THREADS = 1024;
+constexpr int FIN_WAVES = FIN_THREADS / 64;
+constexpr int FIN_LEVELS = 11;                /* passes <= 2^28 / 256 / 1024 = 2^10 */
+static_assert((SROWS & (SROWS - 1)) == 0 && SROWS % 64 == 0 && SROWS >= SW, "summary workgroup shape");
+
+/* `count` floats from src (this workgroup's contiguous share of a [rows][W] plane) into LDS rows of
+   stride LD. vec: src is 16-byte aligned. */
+template <int W, int LD>
+__device__ inline void stage_f32(const float* src, int count, float* dst, bool vec) {
+  const int tid = threadIdx.x;
+  const int nq = vec ? count / 4 : 0;
+  const float4* s4 = reinterpret_cast<const float4*>(src);
+  for (int q = tid; q < nq; q += SROWS) {
+    const float4 v = s4[q];
+    const float x[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int e = 4 * q + c, r = e / W;
+      dst[r * LD + (e - r * W)] = x[c];
+    }
+  }
+  for (int e = 4 * nq + tid; e < count; e += SROWS) {
+    const int r = e / W;
+    dst[r * LD + (e - r * W)] = src[e];
+  }
+}
+
+/* `count` bytes of a uint8 plane into LDS; absent plane: zeros */
+__device__ inline void stage_u8(const uint8_t* src, int count, uint8_t* dst, bool vec) {
+  const int tid = threadIdx.x;
+  if (!src) {
+    if (tid < count) dst[tid] = 0;
+    return;
+  }
+  const int nq = vec ? count / 16 : 0;
+  if (tid < nq) reinterpret_cast<uint4*>(dst)[tid] = reinterpret_cast<const uint4*>(src)[tid];
+  for (int e = 16 * nq + tid; e < count; e += SROWS) dst[e] = src[e];
+}
+
+/* the tree over the 64 lanes' values, adjacent pairs first; the root lands in lane 0 */
+__device__ inline double wave_tree(double x) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) x = x + __shfl_down(x, d);
+  return x;
+}
+
+__global__ __launch_bounds__(SROWS) void summary_kernel(SummaryArgs a) {
+#pragma clang fp contract(off)
+  __shared__ float s_terms[SROWS * S_TERMS_LD];
+  __shared__ float s_cmd[SROWS * S_CMD_LD];
+  __shared__ float s_lp[SROWS * S_LP_LD];
+  __shared__ float s_rew[SROWS], s_val[SROWS], s_tgt[SROWS];
+  __shared__ __attribute__((aligned(16))) uint8_t s_done[SROWS];
+  __shared__ __attribute__((aligned(16))) uint8_t s_succ[SROWS];
+  __shared__ double s_root[SROWS / 64][SW];
+
+  const int tid = threadIdx.x;
+  const size_t row0 = (size_t)blockIdx.x * SROWS;
+  const int nrows = (int)(a.rows - row0 < (size_t)SROWS ? a.rows - row0 : (size_t)SROWS);
+
+  if (a.terms) stage_f32<S_TERMS, S_TERMS_LD>(a.terms + row0 * S_TERMS, nrows * S_TERMS, s_terms, a.vec & 1);
+  if (a.cmd) stage_f32<S_CMD, S_CMD_LD>(a.cmd + row0 * S_CMD, nrows * S_CMD, s_cmd, a.vec & 2);
+  stage_f32<1, 1>(a.reward + row0, nrows, s_rew, a.vec & 4);
+  stage_u8(a.done + row0, nrows, s_done, a.vec & 8);
+  stage_u8(a.success ? a.success + row0 : nullptr, nrows, s_succ, a.vec & 16);
+  if (a.log_prob) stage_f32<S_LP, S_LP_LD>(a.log_prob + row0 * S_LP, nrows * S_LP, s_lp, a.vec & 32);
+  if (a.values) {
+    stage_f32<1, 1>(a.values + row0, nrows, s_val, a.vec & 64);
+    stage_f32<1, 1>(a.targets + row0, nrows, s_tgt, a.vec & 128);
+  }
+  __syncthreads();
+
+  double x[SU];
+#pragma unroll
+  for (int w = 0; w < SU; ++w) x[w] = 0.0; /* rows past the end and null planes: +0.0 leaves */
+  if (tid < nrows) {
+    if (a.terms) {
+#pragma unroll
+      for (int i = 0; i < S_TERMS; ++i) x[ZB_SUM_TERMS + i] = (double)s_terms[tid * S_TERMS_LD + i];
+    }
+    if (a.cmd) {
+#pragma unroll
+      for (int i = 0; i < S_CMD; ++i) x[ZB_SUM_CMD_TERMS + i] = (double)s_cmd[tid * S_CMD_LD + i];
+    }
+    const double r = (double)s_rew[tid];
+    x[ZB_SUM_REWARD] = r;
+    x[ZB_SUM_REWARD_SQ] = r * r;
+    x[ZB_SUM_DONE] = s_done[tid] ? 1.0 : 0.0;
+    x[ZB_SUM_SUCCESS] = s_succ[tid] ? 1.0 : 0.0;
+    if (a.log_prob) {
+      double s = (double)s_lp[tid * S_LP_LD];
+#pragma unroll
+      for (int j = 1; j < S_LP; ++j) s = s + (double)s_lp[tid * S_LP_LD + j];
+      x[ZB_SUM_LOG_PROB] = s;
+    }
+    if (a.values) {
+      const double v = (double)s_val[tid], g = (double)s_tgt[tid], d = g - v;
+      x[ZB_SUM_VALUE] = v;
+      x[ZB_SUM_VALUE_SQ] = v * v;
+      x[ZB_SUM_TARGET] = g;
+      x[ZB_SUM_TARGET_SQ] = g * g;
+      x[ZB_SUM_RESIDUAL_SQ] = d * d;
+    }
+    x[ZB_SUM_ROWS] = 1.0;
+  }
+#pragma unroll
+  for (int w = 0; w < SU; ++w) x[w] = wave_tree(x[w]);
+  if (tid % 64 == 0) {
+#pragma unroll
+    for (int w = 0; w < SU; ++w) s_root[tid / 64][w] = x[w];
+  }
+  __syncthreads();
+  if (tid < SW) {
+    double p = 0.0;
+    if (tid < SU) {
+      constexpr int NW = SROWS / 64;
+      double y[NW];
+#pragma unroll
+      for (int i = 0; i < NW; ++i) y[i] = s_root[i][tid];
+#pragma unroll
+      for (int st = 1; st < NW; st <<= 1)
+#pragma unroll
+        for (int i = 0; i + st < NW; i += 2 * st) y[i] = y[i] + y[i + st];
+      p = y[0];
+    }
+    a.partials[(size_t)blockIdx.x * SW + tid] = p;
+  }
+}
+
+__global__ __launch_bounds__(FIN_THREADS) void summary_finish_kernel(const double* partials, int k, double* out) {
+#pragma clang fp contract(off)
+  __shared__ double s_wave[FIN_WAVES][SW];
+  __shared__ double s_level[FIN_LEVELS][SW];
+  const int tid = threadIdx.x, lane = tid % 64, wv = tid / 64;
+  const int npass = (k + FIN_THREADS - 1) / FIN_THREADS;
+  for (int ps = 0; ps < npass; ++ps) {
+    const int i = ps * FIN_THREADS + tid;
+    double x[SU];
+    if (i < k) {
+      const double* p = partials + (size_t)i * SW;
+#pragma unroll
+      for (int w = 0; w < SU; ++w) x[w] = p[w];
+    } else {
+#pragma unroll
+      for (int w = 0; w < SU; ++w) x[w] = 0.0;
+    }
+#pragma unroll
+    for (int w = 0; w < SU; ++w) x[w] = wave_tree(x[w]);
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < SU; ++w) s_wave[wv][w] = x[w];
+    }
+    __syncthreads();
+    if (tid < SU) {
+      double y[FIN_WAVES];
+#pragma unroll
+      for (int j = 0; j < FIN_WAVES; ++j) y[j] = s_wave[j][tid];
+#pragma unroll
+      for (int st = 1; st < FIN_WAVES; st <<= 1)
+#pragma unroll
+        for (int j = 0; j + st < FIN_WAVES; j += 2 * st) y[j] = y[j] + y[j + st];
+      /* the binary counter: pass ps closes one subtree per trailing 1 bit of ps */
+      double v = y[0];
+      int lv = 0;
+      for (int g = ps; g & 1; g >>= 1, ++lv) v = s_level[lv][tid] + v;
+      s_level[lv][tid] = v; /* lv <= 10: ps < 2^10 */
+    }
+    __syncthreads(); /* s_wave is rewritten by the next pass */
+  }
+  if (tid < SW) {
+    double r = 0.0;
+    if (tid < SU) {
+      /* the open subtrees, smallest (latest) first: each is the right operand of the next larger one */
+      bool have = false;
+      for (int lv = 0; lv < FIN_LEVELS; ++lv) {
+        if ((npass >> lv) & 1) {
+          r = have ? s_level[lv][tid] + r : s_level[lv][tid];
+          have = true;
+        }
+      }
+      r = r + 0.0;
+    }
+    out[tid] = r;
+  }
+}
+
+hipError_t launch_rollout_summary(SummaryArgs a, double* sums_out, hipStream_t s) {
+  const int nblk = (int)((a.rows + SROWS - 1) / SROWS);
+  const void* planes[8] = {a.terms, a.cmd, a.reward, a.done, a.success, a.log_prob, a.values, a.targets};
+  a.vec = 0;
+  for (int p = 0; p < 8; ++p)
+    if (planes[p] && ((uintptr_t)planes[p] % 16) == 0) a.vec |= 1 << p;
+  hipLaunchKernelGGL(summary_kernel, dim3(nblk), dim3(SROWS), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(summary_finish_kernel, dim3(1), dim3(FIN_THREADS), 0, s, a.partials, nblk, sums_out);
+  return hipGetLastError();
 }
 
 hipError_t launch_gae(const GaeArgs& a, double* moments_out, hipStream_t s) {

@@ -316,6 +316,15 @@ class ZbCommandConfig(C.Structure):
     ]
 
 
+# include/zbot_ppo.h "Rollout summary": the words of zb_rollout_summary's sums_out (ZB_SUM_*)
+SUMMARY_WORDS = 32
+SUM_TERMS = 0  # [12]
+SUM_CMD_TERMS = 12  # [5]
+SUM_REWARD, SUM_REWARD_SQ, SUM_DONE, SUM_SUCCESS, SUM_LOG_PROB = 17, 18, 19, 20, 21
+SUM_VALUE, SUM_VALUE_SQ, SUM_TARGET, SUM_TARGET_SQ, SUM_RESIDUAL_SQ, SUM_ROWS = 22, 23, 24, 25, 26, 27
+SUM_USED = 28  # words 28..31 are +0.0
+
+
 class ZbPolicyShape(C.Structure):
     """include/zbot_policy.h "Network shape": the GRU depth and mixture count of a policy handle."""
 

@@ -13,7 +13,7 @@ import os
 from . import cstructs as cs
 
 LIB_NAME = "libzbot_hip.so"
-ABI_VERSION = 4  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch, 4 velocity commands
+ABI_VERSION = 5  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch, 4 velocity commands, 5 the rollout summary (zbot_ppo.h)
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 CSRC_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 
@@ -116,6 +116,13 @@ def load_library(path: str | None = None) -> C.CDLL:
     L.zb_grad_combine_host.argtypes = [vp, C.c_int, C.c_size_t, vp, vp]
     for f in ("zb_ppo_loss", "zb_ppo_loss_host", "zb_grad_sqnorm", "zb_grad_sqnorm_host", "zb_adamw_step",
               "zb_adamw_step_host", "zb_grad_combine", "zb_grad_combine_host"):
+        getattr(L, f).restype = C.c_int
+    # rollout summary (include/zbot_ppo.h "Rollout summary") and its host twin
+    L.zb_rollout_summary_partials_words.argtypes = [C.c_int, C.c_int]
+    L.zb_rollout_summary_partials_words.restype = C.c_size_t
+    L.zb_rollout_summary.argtypes = [vp] * 8 + [C.c_int, C.c_int, vp, vp, vp]
+    L.zb_rollout_summary_host.argtypes = [vp] * 8 + [C.c_int, C.c_int, vp]
+    for f in ("zb_rollout_summary", "zb_rollout_summary_host"):
         getattr(L, f).restype = C.c_int
     # minibatch permutation and gather (include/zbot_ppo.h "Minibatches") and their host twins
     L.zb_minibatch_perm.argtypes = [C.c_uint64, C.c_uint32, C.c_int, vp, vp]

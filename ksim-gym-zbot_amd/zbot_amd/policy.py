@@ -425,7 +425,7 @@ class PolicyRollout:
         self.done = None
 
     def run(self, T: int, record_critic: bool = False, critic: GruPolicy | None = None,
-            critic_carry=None) -> dict:
+            critic_carry=None, record_terms: bool = False, mode: int = SAMPLE) -> dict:
         """T control steps. With record_critic, out["obs_critic"][t] is the critic observation of
         the state the actor acted in at step t (what get_ppo_variables evaluates the critic on,
         train.py:1683-1729) and out["obs_critic_next"] that of the state after step T-1 (the
@@ -437,8 +437,18 @@ class PolicyRollout:
         place) reset where the previous step ended an episode (none at t = 0), then the bootstrap
         V(s_T) (reset where step T-1 ended one). out["value"] [T, n] and out["value_next"] [n] are
         bit-identical to critic.critic(out["obs_critic"], carry, reset=[0, done[:-1]]) followed by
-        critic.critic(out["obs_critic_next"], carry, reset=done[-1]) after the rollout."""
+        critic.critic(out["obs_critic_next"], carry, reset=done[-1]) after the rollout.
+
+        With record_terms, out["reward_terms"] [T, n, 12] holds every step's unscaled reward terms
+        (cs.TERM_NAMES; zb_step's reward_terms output), row 0 with ksim's FeetAirtime term when
+        exact_airtime is on, as out["reward"][0] has it; with a command config on the engine,
+        out["command_terms"] [T, n, 5] holds the tracking terms (cs.CMD_TERM_NAMES), read with
+        zb_get_command_terms on the group's own stream right after each step. Every other output
+        keeps its bits. `mode`: SAMPLE, or MODE for the deterministic rollout of the mixture's mode
+        (the actor's log-probs are then those of the mode actions)."""
         torch = self.actor.torch
+        if mode not in (SAMPLE, MODE):
+            raise ZbError("PolicyRollout.run: mode is SAMPLE or MODE")
         n, dev = self.eng.n, self.eng.device
         if self.obs is None:
             self.reset()
@@ -461,6 +471,11 @@ class PolicyRollout:
                 raise ZbError("an in-loop critic needs record_critic=True, a critic handle and its carry")
             critic._check_carry(critic_carry, n)
             val = torch.empty(T + 1, n, **f32)
+        terms = cterms = None
+        if record_terms:
+            terms = torch.empty(T, n, cs.NUM_TERMS, **f32)
+            if getattr(self.eng, "command_cfg", None) is not None:
+                cterms = torch.empty(T, n, cs.NUM_CMD_TERMS, **f32)
         L = self.eng.L
         # an EnvGroups engine runs each group's actor -> zb_step chain on the group's own stream
         # (DESIGN.md §4f); a HipEngine is one group on the current stream
@@ -478,19 +493,23 @@ class PolicyRollout:
                     r = done[t - 1][lo:hi] if t > 0 else (None if self.done is None else self.done[lo:hi])
                     if self.stagger and grouped and t == 0 and g > 0:
                         s.wait_event(prev_actor)
-                    self.actor.actor(obs[t][lo:hi], self.carry[lo:hi], reset=r, mode=SAMPLE, seed=self.seed,
+                    self.actor.actor(obs[t][lo:hi], self.carry[lo:hi], reset=r, mode=mode, seed=self.seed,
                                      env_offset=e.env_offset, step=self.step_count, actions=acts[t][lo:hi],
                                      log_prob=lp[t][lo:hi])
                     if self.stagger and grouped and t == 0:
                         prev_actor = torch.cuda.Event()
                         prev_actor.record(s)
                     _check(L.zb_step(e.h, acts[t][lo:hi].data_ptr(), obs[t + 1][lo:hi].data_ptr(),
-                                     crit[t + 1][lo:hi].data_ptr() if record_critic else None, None, None,
+                                     crit[t + 1][lo:hi].data_ptr() if record_critic else None, None,
+                                     terms[t][lo:hi].data_ptr() if record_terms else None,
                                      rew[t][lo:hi].data_ptr(), done[t][lo:hi].data_ptr(),
                                      success[t][lo:hi].data_ptr(), float(self.curriculum), stream))
+                    if cterms is not None:
+                        _check(L.zb_get_command_terms(e.h, cterms[t][lo:hi].data_ptr(), stream))
                     if self.exact_airtime and t == T - 1:
-                        _check(L.zb_feet_airtime_exact(e.h, rew[0][lo:hi].data_ptr(), None, float(self.curriculum),
-                                                       stream))
+                        _check(L.zb_feet_airtime_exact(e.h, rew[0][lo:hi].data_ptr(),
+                                                       terms[0][lo:hi].data_ptr() if record_terms else None,
+                                                       float(self.curriculum), stream))
                     if critic is not None:  # V(s_t): its input crit[t] is ready since step t-1
                         critic.critic(crit[t][lo:hi], critic_carry[lo:hi],
                                       reset=done[t - 1][lo:hi] if t > 0 else None, value=val[t][lo:hi])
@@ -512,4 +531,8 @@ class PolicyRollout:
         if critic is not None:
             out["value"] = val[:T]
             out["value_next"] = val[T]
+        if record_terms:
+            out["reward_terms"] = terms
+            if cterms is not None:
+                out["command_terms"] = cterms
         return out

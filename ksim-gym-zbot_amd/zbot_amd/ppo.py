@@ -260,6 +260,96 @@ def grad_sqnorm(grad, out=None, partials=None):
     return out
 
 
+SUMMARY_WORDS = 32  # ZB_SUMMARY_WORDS
+_SUMMARY_PLANES = (("reward_terms", 12), ("command_terms", 5), ("reward", 0), ("done", 0), ("success", 0),
+                   ("log_prob", JOINTS), ("values", 0), ("value_targets", 0))  # name, trailing axis (0: none)
+_summary_partials: dict = {}  # (device, words) -> scratch, reused between calls on one stream
+
+
+def _summary_shapes(planes: dict, shape_of):
+    """(T, n) of the planes of a rollout summary, each checked against [T, n(, k)]."""
+    if planes["reward"] is None or planes["done"] is None:
+        raise ZbError("rollout_summary needs reward and done")
+    if (planes["values"] is None) != (planes["value_targets"] is None):
+        raise ZbError("rollout_summary: values and value_targets go together (both or neither)")
+    rs = tuple(shape_of(planes["reward"]))
+    if len(rs) != 2 or rs[0] < 1 or rs[1] < 1:
+        raise ZbError(f"reward must be [T, n] with T, n >= 1, got {list(rs)}")
+    T, n = rs
+    for name, k in _SUMMARY_PLANES:
+        t = planes[name]
+        want = (T, n, k) if k else (T, n)
+        if t is not None and tuple(shape_of(t)) != want:
+            raise ZbError(f"{name} must be {list(want)}, got {list(shape_of(t))}")
+    return T, n
+
+
+def rollout_summary(reward, done, success=None, reward_terms=None, command_terms=None, log_prob=None, values=None,
+                    value_targets=None, out=None, partials=None):
+    """zb_rollout_summary: the 32 fp64 sums of a rollout (cstructs.SUM_*; include/zbot_ppo.h "Rollout
+    summary") by the fixed pairwise tree over the T n rows in (t, env) order, on the GPU,
+    asynchronously on the current stream. reward [T, n] float32, done / success [T, n] uint8,
+    reward_terms [T, n, 12], command_terms [T, n, 5], log_prob [T, n, 20], values / value_targets
+    [T, n] float32 (both or neither): contiguous device tensors (views at any element offset are
+    fine); the words of an absent plane are +0.0. -> out [32] float64. `out` and the `partials`
+    scratch are reused when given; without `partials` one scratch per device and size is kept and
+    reused (calls on different streams of a device should pass their own)."""
+    import torch  # noqa: PLC0415
+
+    L = load_library()
+    if not isinstance(reward, torch.Tensor):
+        raise ZbError("reward must be a float32 device tensor")
+    dev = reward.device
+    if dev.type != "cuda":
+        raise ZbError("ppo.rollout_summary runs on the GPU (libzbot_hip.so); rollout_summary_host is the CPU twin")
+    planes = dict(reward_terms=reward_terms, command_terms=command_terms, reward=reward, done=done, success=success,
+                  log_prob=log_prob, values=values, value_targets=value_targets)
+    T, n = _summary_shapes(planes, lambda t: t.shape)
+    for name, _ in _SUMMARY_PLANES:
+        t = planes[name]
+        if t is None:
+            continue
+        dt = torch.uint8 if name in ("done", "success") else torch.float32
+        if not isinstance(t, torch.Tensor) or t.dtype != dt or t.device != dev or not t.is_contiguous():
+            raise ZbError(f"{name} must be a contiguous {dt} tensor on {dev}")
+    words = int(L.zb_rollout_summary_partials_words(T, n))
+    if words == 0:
+        raise ZbError(f"rollout_summary: T * n = {T} * {n} rows (1 to 2^28)")
+    if partials is None:
+        partials = _summary_partials.get((dev, words))
+        if partials is None:
+            partials = _summary_partials[(dev, words)] = torch.empty(words, dtype=torch.float64, device=dev)
+    else:
+        _f64_dev(partials, dev, torch, "partials", words)
+    out = (torch.empty(SUMMARY_WORDS, dtype=torch.float64, device=dev) if out is None
+           else _f64_dev(out, dev, torch, "out", SUMMARY_WORDS))
+    p = lambda name: None if planes[name] is None else planes[name].data_ptr()  # noqa: E731
+    with torch.cuda.device(dev):
+        _check(L.zb_rollout_summary(*(p(name) for name, _ in _SUMMARY_PLANES), T, n, partials.data_ptr(),
+                                    out.data_ptr(), _stream(torch, dev)))
+    return out[:SUMMARY_WORDS]
+
+
+def rollout_summary_host(reward, done, success=None, reward_terms=None, command_terms=None, log_prob=None,
+                         values=None, value_targets=None):
+    """zb_rollout_summary_host: the same leaves and the same tree on the CPU (numpy arrays or CPU
+    tensors in, a float64 tensor [32] out): the kernel's bit reference."""
+    import numpy as np  # noqa: PLC0415
+    import torch  # noqa: PLC0415
+
+    planes = dict(reward_terms=reward_terms, command_terms=command_terms, reward=reward, done=done, success=success,
+                  log_prob=log_prob, values=values, value_targets=value_targets)
+    for name, _ in _SUMMARY_PLANES:
+        if planes[name] is not None:
+            planes[name] = _host(planes[name], np.uint8 if name in ("done", "success") else np.float32, name)
+    T, n = _summary_shapes(planes, lambda a: a.shape)
+    out = np.empty(SUMMARY_WORDS, np.float64)
+    _check(load_library().zb_rollout_summary_host(
+        *(None if planes[name] is None else planes[name].ctypes.data for name, _ in _SUMMARY_PLANES), T, n,
+        out.ctypes.data))
+    return torch.from_numpy(out)
+
+
 COMBINE_MAX_WORLD = 64  # ZB_COMBINE_MAX_WORLD
 
 

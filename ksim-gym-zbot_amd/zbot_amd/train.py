@@ -4,8 +4,9 @@ update in HIP, the episode-length curriculum.
 
     tr = Trainer(engine, actor, critic, rollout_steps=200, num_passes=4, batch_size=128,
                  seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, group=None,
-                 command_config=None, **learner_kw)
-    m = tr.step()            # one iteration; returns metrics
+                 command_config=None, telemetry=False, **learner_kw)
+    m = tr.step()            # one iteration; returns metrics (telemetry=True: with m["telemetry"])
+    v = tr.validate()        # a rollout without an update: its telemetry; the Trainer stays where it was
     sd = tr.state_dict(); tr.load_state_dict(sd)
 
 Several GPUs: one Trainer per rank over its shard of the envs (engine.env_offset = rank x engine.n)
@@ -29,6 +30,10 @@ One step(), in order:
   6. curriculum.rollout_episode_length and curriculum.update: the iteration's one host
      synchronisation is that float;
   7. the new level goes to the next rollout.
+With telemetry=True the rollout of 3. also records the reward and command terms, and between 4. and
+5. one ppo.rollout_summary on the current stream reduces them, the rewards, the episode ends, the
+log-probs, the values and the value targets to 32 sums; telemetry=False issues none
+of this.
 """
 
 from __future__ import annotations
@@ -40,9 +45,9 @@ from . import cstructs as cs
 from . import ppo
 from .curriculum import CurriculumState, EpisodeLengthCurriculum, rollout_episode_length
 from .engine import ZbError
-from .metrics import command_term_means
+from .metrics import command_term_means, rollout_telemetry
 from .learner import DEFAULT_BATCH_SIZE, DEFAULT_NUM_PASSES, HipPpoLearner
-from .policy import ACTOR, GruPolicy, PolicyRollout, PolicyShape
+from .policy import ACTOR, MODE, SAMPLE, GruPolicy, PolicyRollout, PolicyShape
 
 DEFAULT_ROLLOUT_STEPS = 200  # rollout_length_seconds 4.0 / ctrl_dt 0.02 (train.py:1775, 1783)
 
@@ -57,8 +62,15 @@ class Trainer:
     def __init__(self, engine, actor: GruPolicy, critic: GruPolicy, rollout_steps: int = DEFAULT_ROLLOUT_STEPS,
                  num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, seed: int = 0,
                  shuffle: bool = True, curriculum: EpisodeLengthCurriculum | None = None, ctrl_dt: float = 0.02,
-                 group=None, command_config: cs.ZbCommandConfig | None = None, **learner_kw):
-        """command_config: a config.command_config(...): the engine samples velocity commands
+                 group=None, command_config: cs.ZbCommandConfig | None = None, telemetry: bool = False,
+                 **learner_kw):
+        """telemetry: step() also returns "telemetry", metrics.rollout_telemetry of the rollout's
+        sums (every reward and command term, how episodes end, the entropy estimate, the explained
+        variance, the episode statistics). On several ranks the 32 sums go through
+        dist.reduce_fixed_order: every rank then reports the same bits, but they are a rank-order
+        sum of per-rank trees, not the tree over all rows: not the bits a single rank over the same
+        envs reports. The weights do not depend on it.
+        command_config: a config.command_config(...): the engine samples velocity commands
         (include/zbot_command.h) and adds the tracking terms to the reward; step() then reports
         the per-term means. It is set on the engine here and is part of state_dict()."""
         if actor.kind != ACTOR or critic.kind == ACTOR:
@@ -82,6 +94,7 @@ class Trainer:
             agree(dict(seed=self.seed % (1 << 63), shuffle=int(self.shuffle), rollout_steps=self.T,
                        num_passes=self.num_passes, batch_size=self.batch_size, envs_per_rank=int(engine.n)),
                   f"Trainer over {self.world} ranks", group)
+        self.telemetry = bool(telemetry)
         self.command_config = command_config
         if command_config is not None:
             engine.set_command_config(command_config)  # before the rollout's first reset draws the commands
@@ -107,7 +120,8 @@ class Trainer:
         """One training iteration. Returns {"iteration", "level" (the level the rollout ran at),
         "episode_length" (seconds, a float), "reward" (mean per env-step, over all ranks), "loss", "clip_fraction",
         "approx_kl" ([optimizer steps] each), "sums" (HipPpoLearner.update's list), and with a command
-        config "command_terms" (metrics.command_term_means of the rollout's last step)}; the tensors are
+        config "command_terms" (metrics.command_term_means of the rollout's last step), and with
+        telemetry=True "telemetry" (metrics.rollout_telemetry: a dict of 0-d tensors)}; the tensors are
         on the device and nothing but the episode length is synchronised."""
         torch = self.torch
         ro, T = self.rollout, self.T
@@ -119,12 +133,16 @@ class Trainer:
         level = self.cur_state.level
         ro.curriculum = level
         self._mark("rollout", False)
-        out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry)
+        if self.telemetry:
+            out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry, record_terms=True)
+        else:
+            out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry)
         self._mark("rollout", True)
         self._mark("ppo_inputs", False)
         inputs = ppo.compute_ppo_inputs(out["value"], out["reward"], out["done"], out["success"],
                                         bootstrap=out["value_next"], group=self.group)
         self._mark("ppo_inputs", True)
+        tsums = self._summary(out, inputs) if self.telemetry else None
         reset = None
         if prev_done is not None:
             reset = torch.cat([prev_done[None], out["done"][:T - 1]])
@@ -132,7 +150,8 @@ class Trainer:
         sums = self.learner.update(out, inputs, self.actor, self.critic, carry0, ccarry0, reset=reset,
                                    num_passes=self.num_passes, batch_size=self.batch_size)
         self._mark("update", True)
-        length = rollout_episode_length(self.eng.get_stats(), self.eng.get_state(), out["done"][T - 1], self.ctrl_dt,
+        stats = self.eng.get_stats()
+        length = rollout_episode_length(stats, self.eng.get_state(), out["done"][T - 1], self.ctrl_dt,
                                         group=self.group)
         self.cur_state = self.curriculum.update(self.cur_state, length)
         self.iteration += 1
@@ -150,9 +169,74 @@ class Trainer:
         if self.command_config is not None:
             # the rollout's last step, mean over this rank's envs (zbot_amd.metrics)
             extra["command_terms"] = command_term_means(self.eng.get_command_terms())
+        if self.telemetry:
+            extra["telemetry"] = self._telemetry(tsums, stats, level)
         return dict(iteration=self.iteration, level=level, episode_length=length, reward=reward, **extra,
                     loss=-s[:, 0] / s[:, 4] + s[:, 5] * 0.5 * s[:, 1] / s[:, 4], clip_fraction=s[:, 2] / s[:, 4],
                     approx_kl=s[:, 3] / s[:, 4], sums=sums)
+
+    def _summary(self, out: dict, inputs):
+        """ppo.rollout_summary of a recorded rollout and its PPO inputs, on the current stream."""
+        return ppo.rollout_summary(out["reward"], out["done"], out["success"], reward_terms=out.get("reward_terms"),
+                                   command_terms=out.get("command_terms"), log_prob=out["log_prob"],
+                                   values=out["value"], value_targets=inputs.value_targets_t)
+
+    def _telemetry(self, sums, stats, level: float) -> dict:
+        """metrics.rollout_telemetry of this rank's sums and statistics window; over several ranks
+        both are summed in rank order first (one collective), so every rank returns the same bits."""
+        if self.world > 1:
+            from .dist import reduce_fixed_order  # noqa: PLC0415
+
+            tot = reduce_fixed_order(self.torch.cat([sums, stats.double().sum(0)]), group=self.group)
+            sums, stats = tot[:cs.SUMMARY_WORDS], tot[cs.SUMMARY_WORDS:][None]
+        return rollout_telemetry(sums, self.eng.cfg, level, command_config=self.command_config, stats=stats,
+                                 ctrl_dt=self.ctrl_dt)
+
+    def validate(self, steps: int | None = None, mode: str = "sample") -> dict:
+        """ksim's validation rollout (valid_every_n_steps, train.py:1783): one rollout of `steps`
+        control steps (default: rollout_steps) at the current level with no update and no
+        curriculum step; returns its telemetry (metrics.rollout_telemetry; the values are the in-loop
+        critic's, the value targets ppo.compute_ppo_inputs'). mode "sample" draws actions as training
+        does (from the Trainer's seed and step count: the rollout the next step() would start with),
+        "mode" takes the mixture's mode: a deterministic rollout, whose log-probs, and with them
+        entropy_estimate, are those of the mode actions.
+
+        The Trainer is left exactly where it was: the engine's state rows (which hold the velocity
+        commands, the airtime words and the RNG counters) and randomisation rows, the rollout's
+        obs, obs_c, done, actor carry and step count and the critic carry are copied before the run
+        and put back after it. The statistics window is cleared before the run and read after it;
+        step() clears it at its own start, so no iteration loses anything. Works on a HipEngine and
+        on an EnvGroups. Over several ranks every rank calls it (the advantage moments and the
+        telemetry sums are collectives)."""
+        modes = {"sample": SAMPLE, "mode": MODE}
+        if mode not in modes:
+            raise ZbError(f"validate(mode=...): 'sample' or 'mode', got {mode!r}")
+        T = self.T if steps is None else int(steps)
+        if T < 1:
+            raise ZbError("validate: steps must be >= 1")
+        ro, eng = self.rollout, self.eng
+        if ro.obs is None:
+            ro.reset()
+        c = lambda t: None if t is None else t.clone()  # noqa: E731
+        state, rand = eng.get_state(), eng.get_rand()
+        saved = (c(ro.obs), c(ro.obs_c), c(ro.done), ro.carry.clone(), int(ro.step_count), self.critic_carry.clone(),
+                 ro.curriculum)
+        level = self.cur_state.level
+        ro.curriculum = level
+        eng.get_stats(clear=True)
+        out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry, record_terms=True,
+                     mode=modes[mode])
+        inputs = ppo.compute_ppo_inputs(out["value"], out["reward"], out["done"], out["success"],
+                                        bootstrap=out["value_next"], group=self.group)
+        tel = self._telemetry(self._summary(out, inputs), eng.get_stats(), level)
+        eng.set_state(state)
+        eng.set_rand(rand)
+        ro.obs, ro.obs_c, ro.done = saved[0], saved[1], saved[2]
+        ro.carry.copy_(saved[3])
+        ro.step_count = saved[4]
+        self.critic_carry.copy_(saved[5])
+        ro.curriculum = saved[6]
+        return tel
 
     def state_dict(self) -> dict:
         """Everything a fresh process needs to continue with the same bits (copies): the engine's
