@@ -244,6 +244,37 @@ int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int 
                              uint64_t seed, uint32_t epoch);
 
 /*
+ * ---- Chunked minibatches: the gather of truncated BPTT with stored carries ----
+ * Added in ABI version 6 (zb_minibatch_gather_seq, zb_minibatch_gather_seq_host).
+ *
+ * A rollout of T steps is cut into C = T / seq_len chunks of L = seq_len steps, and every env of
+ * a minibatch contributes its C chunks as C sequences: the networks then run on [L, C count]
+ * instead of [T, count]. The envs of the minibatch are the same as without chunks: positions
+ * [lo, lo + count) of the same permutation p over the n envs.
+ *
+ * zb_minibatch_gather_seq is zb_minibatch_gather with one more law. cut[k] != 0 marks item k as a
+ * time item: its rows (= T, a multiple of seq_len) are cut in chunks, and for l < L, c < C,
+ * j < count
+ *   dst[l][c count + j][:] = src[c L + l][p(lo + j)][:]
+ * with dst dense [L][C count][row_bytes] (the same bytes in all as [rows][count][row_bytes]).
+ * cut[k] == 0 leaves item k to zb_minibatch_gather's law dst[r][j] = src[r][p(lo + j)]: the
+ * carries stored at the chunk starts are such an item with rows = C, whose destination
+ * [C][count][...] read as C count sequences has the same column order q = c count + j; a
+ * whole-run carry is one with rows = 1. Column q of every item is so chunk c of env p(lo + j).
+ * With seq_len == rows a time item moves as in zb_minibatch_gather.
+ *
+ * Everything else is zb_minibatch_gather's: the explicit source time stride, src == NULL
+ * zero-fills, the access width per item, `items` and `cut` host arrays read during the call,
+ * asynchronous on `stream`, nothing allocated. Bad arguments (zb_minibatch_gather's, a null cut,
+ * seq_len < 1, a time item whose rows are no multiple of seq_len) return ZB_EARG and launch
+ * nothing.
+ */
+int zb_minibatch_gather_seq(const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len, int n, int lo,
+                            int count, int shuffle, uint64_t seed, uint32_t epoch, void* stream);
+int zb_minibatch_gather_seq_host(const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len, int n,
+                                 int lo, int count, int shuffle, uint64_t seed, uint32_t epoch);
+
+/*
  * ---- Rollout summary: every sum a rollout's telemetry needs, in one fixed-order reduction ----
  * Added in ABI version 5 (zb_rollout_summary_partials_words, zb_rollout_summary,
  * zb_rollout_summary_host).

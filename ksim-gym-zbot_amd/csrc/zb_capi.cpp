@@ -23,7 +23,7 @@ using zb::check_cfg;
 using zb::check_model;
 using zb::fail;
 
-#define ZB_ABI_VERSION 5
+#define ZB_ABI_VERSION 6
 
 struct ZbHandle {
   int device;
@@ -612,11 +612,9 @@ int zb_minibatch_perm(uint64_t seed, uint32_t epoch, int n, int32_t* perm, void*
   return ZB_OK;
 }
 
-int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
-                        uint64_t seed, uint32_t epoch, void* stream) {
-  zb::GatherArgs a;
-  memset(&a, 0, sizeof a);
-  if (int rc = zb::check_gather_args("zb_minibatch_gather", items, n_items, n, lo, count, a.it)) return rc;
+/* the launch of both gathers, on items already checked into a.it */
+static int gather_launch(const char* what, zb::GatherArgs& a, int n_items, int n, int lo, int count, int shuffle,
+                         uint64_t seed, uint32_t epoch, void* stream) {
   a.n_items = n_items;
   a.n = n;
   a.lo = lo;
@@ -625,8 +623,25 @@ int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, i
   a.epoch = epoch;
   a.seed = seed;
   hipError_t e = zb::launch_minibatch_gather(a, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ZB_ELAUNCH, "zb_minibatch_gather launch: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(ZB_ELAUNCH, "%s launch: %s", what, hipGetErrorString(e));
   return ZB_OK;
+}
+
+int zb_minibatch_gather(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                        uint64_t seed, uint32_t epoch, void* stream) {
+  zb::GatherArgs a;
+  memset(&a, 0, sizeof a);
+  if (int rc = zb::check_gather_args("zb_minibatch_gather", items, n_items, n, lo, count, a.it)) return rc;
+  return gather_launch("zb_minibatch_gather", a, n_items, n, lo, count, shuffle, seed, epoch, stream);
+}
+
+int zb_minibatch_gather_seq(const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len, int n, int lo,
+                            int count, int shuffle, uint64_t seed, uint32_t epoch, void* stream) {
+  zb::GatherArgs a;
+  memset(&a, 0, sizeof a);
+  if (int rc = zb::check_gather_seq_args("zb_minibatch_gather_seq", items, cut, n_items, seq_len, n, lo, count, a.it))
+    return rc;
+  return gather_launch("zb_minibatch_gather_seq", a, n_items, n, lo, count, shuffle, seed, epoch, stream);
 }
 
 /* ---- GRU policy / value networks (include/zbot_policy.h) ---- */

@@ -472,6 +472,21 @@ int check_gather_args(const char* what, const ZbGatherItem* items, int n_items, 
     o.row_bytes = it.row_bytes;
     o.stride = (long long)it.src_t_stride_bytes;
     o.width = !(bits & 15) ? 16 : (!(bits & 7) ? 8 : (!(bits & 3) ? 4 : 1));
+    o.chunk = 0;
+  }
+  return ZB_OK;
+}
+
+int check_gather_seq_args(const char* what, const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len,
+                          int n, int lo, int count, GatherItemDev* out) {
+  if (int rc = check_gather_args(what, items, n_items, n, lo, count, out)) return rc;
+  if (!cut) return fail(ZB_EARG, "%s: null cut", what);
+  if (seq_len < 1) return fail(ZB_EARG, "%s: seq_len = %d (at least 1)", what, seq_len);
+  for (int k = 0; k < n_items; k++) {
+    if (!cut[k]) continue;
+    if (out[k].rows % seq_len)
+      return fail(ZB_EARG, "%s: item %d: rows = %d is no multiple of seq_len = %d", what, k, out[k].rows, seq_len);
+    out[k].chunk = seq_len;
   }
   return ZB_OK;
 }
@@ -643,24 +658,43 @@ int zb_minibatch_perm_host(uint64_t seed, uint32_t epoch, int n, int32_t* perm) 
   return ZB_OK;
 }
 
-int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
-                             uint64_t seed, uint32_t epoch) {
-  zb::GatherItemDev it[ZB_GATHER_MAX_ITEMS];
-  if (int rc = zb::check_gather_args("zb_minibatch_gather_host", items, n_items, n, lo, count, it)) return rc;
+/* both gathers on checked items: source row t = c L + l of an item cut in chunks of L = chunk rows
+   (C = rows / L of them) lands in destination row l C + c, any other row t in row t */
+static void gather_host(const zb::GatherItemDev* it, int n_items, int n, int lo, int count, int shuffle,
+                        uint64_t seed, uint32_t epoch) {
   std::vector<uint32_t> p((size_t)count);
   for (int j = 0; j < count; j++)
     p[j] = shuffle ? zbf_perm_index(seed, epoch, (uint32_t)n, (uint32_t)(lo + j)) : (uint32_t)(lo + j);
   for (int k = 0; k < n_items; k++) {
     const size_t rb = (size_t)it[k].row_bytes;
-    for (int t = 0; t < it[k].rows; t++)
+    const int L = it[k].chunk, C = L ? it[k].rows / L : 0;
+    for (int t = 0; t < it[k].rows; t++) {
+      const int dt = L ? (t % L) * C + t / L : t;
       for (int j = 0; j < count; j++) {
-        char* d = it[k].dst + ((size_t)t * (size_t)count + (size_t)j) * rb;
+        char* d = it[k].dst + ((size_t)dt * (size_t)count + (size_t)j) * rb;
         if (it[k].src)
           memcpy(d, it[k].src + (size_t)t * (size_t)it[k].stride + (size_t)p[j] * rb, rb);
         else
           memset(d, 0, rb);
       }
+    }
   }
+}
+
+int zb_minibatch_gather_host(const ZbGatherItem* items, int n_items, int n, int lo, int count, int shuffle,
+                             uint64_t seed, uint32_t epoch) {
+  zb::GatherItemDev it[ZB_GATHER_MAX_ITEMS];
+  if (int rc = zb::check_gather_args("zb_minibatch_gather_host", items, n_items, n, lo, count, it)) return rc;
+  gather_host(it, n_items, n, lo, count, shuffle, seed, epoch);
+  return ZB_OK;
+}
+
+int zb_minibatch_gather_seq_host(const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len, int n,
+                                 int lo, int count, int shuffle, uint64_t seed, uint32_t epoch) {
+  zb::GatherItemDev it[ZB_GATHER_MAX_ITEMS];
+  if (int rc = zb::check_gather_seq_args("zb_minibatch_gather_seq_host", items, cut, n_items, seq_len, n, lo, count, it))
+    return rc;
+  gather_host(it, n_items, n, lo, count, shuffle, seed, epoch);
   return ZB_OK;
 }
 

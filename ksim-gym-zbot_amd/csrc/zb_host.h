@@ -107,10 +107,14 @@ struct GatherItemDev {
   const char* src;
   char* dst;
   int rows, row_bytes, width;
+  int chunk; /* 0, or zb_minibatch_gather_seq's seq_len for a time item (fills the padding in front of stride) */
   long long stride;
 };
 int check_gather_args(const char* what, const ZbGatherItem* items, int n_items, int n, int lo, int count,
                       GatherItemDev* out);
+/* zb_minibatch_gather_seq / _host: check_gather_args, then seq_len and the time items' rows */
+int check_gather_seq_args(const char* what, const ZbGatherItem* items, const int32_t* cut, int n_items, int seq_len,
+                          int n, int lo, int count, GatherItemDev* out);
 
 }  // namespace zb
 

@@ -14,10 +14,17 @@
  *                  same for every thread of a workgroup, so the switch on it does not diverge.
  *                  The time rows of an item are strided over gridDim.z; items with fewer rows
  *                  than the launch's largest leave the extra workgroups with nothing to do.
+ *                  gather_kernel<true> is zb_minibatch_gather_seq's: source row t = c L + l of an
+ *                  item cut in chunks of L rows (C = rows / L of them) goes to destination row
+ *                  l C + c, so dst [L][C count] holds chunk c of the workgroup's envs in columns
+ *                  c count + j; only the row's base address differs, the row still moves as one
+ *                  contiguous piece. gather_kernel<false> is the whole-sequence gather as it was.
  *
  * Bounds: a workgroup reads src rows p(lo + j) < n for j < count and t < rows, and writes dst rows
- * t * count + j; zbf_perm_index returns a value < n for an index < n, and lo + count <= n is checked
- * before the launch.
+ * t' * count + j with t' = t, or for a cut item t' = l C + c < L C = rows (l < L, c < C; rows is a
+ * multiple of L, checked before the launch): the same [rows][count] extent either way.
+ * zbf_perm_index returns a value < n for an index < n, and lo + count <= n is checked before the
+ * launch.
  */
 #include <hip/hip_runtime.h>
 
@@ -35,7 +42,7 @@ __global__ __launch_bounds__(256) void perm_kernel(uint64_t seed, uint32_t epoch
   if (i < n) perm[i] = (int32_t)zbf_perm_index(seed, epoch, (uint32_t)n, (uint32_t)i);
 }
 
-template <typename V>
+template <typename V, bool SEQ>
 __device__ inline void move_rows(const GatherItemDev& it, const uint32_t* sp, int j0, int jn, int count) {
   const int upr = it.row_bytes / (int)sizeof(V); /* units per row */
   const int units = jn * upr;
@@ -43,7 +50,12 @@ __device__ inline void move_rows(const GatherItemDev& it, const uint32_t* sp, in
   __builtin_memset(&zero, 0, sizeof(V));
   for (int t = blockIdx.z; t < it.rows; t += gridDim.z) {
     const char* s = it.src ? it.src + (size_t)t * (size_t)it.stride : nullptr;
-    char* d = it.dst + ((size_t)t * (size_t)count + (size_t)j0) * (size_t)it.row_bytes;
+    int dt = t;
+    if (SEQ && it.chunk) { /* uniform over the workgroup */
+      const int c = t / it.chunk;
+      dt = (t - c * it.chunk) * (it.rows / it.chunk) + c;
+    }
+    char* d = it.dst + ((size_t)dt * (size_t)count + (size_t)j0) * (size_t)it.row_bytes;
     for (int u = threadIdx.x; u < units; u += GTHREADS) {
       const int j = u / upr, k = u - j * upr;
       V x = zero;
@@ -53,6 +65,7 @@ __device__ inline void move_rows(const GatherItemDev& it, const uint32_t* sp, in
   }
 }
 
+template <bool SEQ>
 __global__ __launch_bounds__(GTHREADS) void gather_kernel(GatherArgs a) {
   __shared__ uint32_t sp[GJ];
   const GatherItemDev& it = a.it[blockIdx.y];
@@ -65,10 +78,10 @@ __global__ __launch_bounds__(GTHREADS) void gather_kernel(GatherArgs a) {
   }
   __syncthreads();
   switch (it.width) {
-    case 16: move_rows<uint4>(it, sp, j0, jn, a.count); break;
-    case 8: move_rows<uint2>(it, sp, j0, jn, a.count); break;
-    case 4: move_rows<uint32_t>(it, sp, j0, jn, a.count); break;
-    default: move_rows<uint8_t>(it, sp, j0, jn, a.count); break;
+    case 16: move_rows<uint4, SEQ>(it, sp, j0, jn, a.count); break;
+    case 8: move_rows<uint2, SEQ>(it, sp, j0, jn, a.count); break;
+    case 4: move_rows<uint32_t, SEQ>(it, sp, j0, jn, a.count); break;
+    default: move_rows<uint8_t, SEQ>(it, sp, j0, jn, a.count); break;
   }
 }
 
@@ -78,10 +91,16 @@ hipError_t launch_minibatch_perm(uint64_t seed, uint32_t epoch, int n, int32_t* 
 }
 
 hipError_t launch_minibatch_gather(const GatherArgs& a, hipStream_t s) {
-  int rows = 1;
-  for (int k = 0; k < a.n_items; k++) rows = a.it[k].rows > rows ? a.it[k].rows : rows;
+  int rows = 1, seq = 0;
+  for (int k = 0; k < a.n_items; k++) {
+    rows = a.it[k].rows > rows ? a.it[k].rows : rows;
+    seq |= a.it[k].chunk;
+  }
   const dim3 grid((unsigned)((a.count + GJ - 1) / GJ), (unsigned)a.n_items, (unsigned)(rows < GMAX_Z ? rows : GMAX_Z));
-  hipLaunchKernelGGL(gather_kernel, grid, dim3(GTHREADS), 0, s, a);
+  if (seq)
+    hipLaunchKernelGGL(gather_kernel<true>, grid, dim3(GTHREADS), 0, s, a);
+  else
+    hipLaunchKernelGGL(gather_kernel<false>, grid, dim3(GTHREADS), 0, s, a);
   return hipGetLastError();
 }
 

@@ -13,7 +13,7 @@ import os
 from . import cstructs as cs
 
 LIB_NAME = "libzbot_hip.so"
-ABI_VERSION = 5  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch, 4 velocity commands, 5 the rollout summary (zbot_ppo.h)
+ABI_VERSION = 6  # include/zbot.h: 2 added zb_step / zb_rollout's `success`, 3 the exact FeetAirtime patch, 4 velocity commands, 5 the rollout summary (zbot_ppo.h), 6 the chunked minibatch gather (zbot_ppo.h)
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 CSRC_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
 
@@ -130,7 +130,11 @@ def load_library(path: str | None = None) -> C.CDLL:
     gather_args = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32]
     L.zb_minibatch_gather.argtypes = gather_args + [vp]
     L.zb_minibatch_gather_host.argtypes = gather_args
-    for f in ("zb_minibatch_perm", "zb_minibatch_perm_host", "zb_minibatch_gather", "zb_minibatch_gather_host"):
+    seq_args = [vp, vp, C.c_int, C.c_int] + gather_args[2:]  # items, cut, n_items, seq_len, then as above
+    L.zb_minibatch_gather_seq.argtypes = seq_args + [vp]
+    L.zb_minibatch_gather_seq_host.argtypes = seq_args
+    for f in ("zb_minibatch_perm", "zb_minibatch_perm_host", "zb_minibatch_gather", "zb_minibatch_gather_host",
+              "zb_minibatch_gather_seq", "zb_minibatch_gather_seq_host"):
         getattr(L, f).restype = C.c_int
     # GRU actor / critic (include/zbot_policy.h)
     L.zb_policy_param_count.argtypes = [C.c_int]

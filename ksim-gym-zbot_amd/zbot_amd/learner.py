@@ -182,6 +182,65 @@ class _ShuffledMinibatches:
         ppo.gather_minibatch(items, n, lo, count, shuffle_seed=seed, epoch=epoch)
         return b
 
+    def cut_chunks(self, torch, rollout, ppo_inputs, reset, T, n, lo, count, seed, epoch, seq_len) -> dict:
+        """The same minibatch as C = T / seq_len sequences of L = seq_len steps per env (truncated
+        BPTT), by one ppo.gather_minibatch(seq_len=) launch: every [T, n] array as
+        [L, C count], column c count + j chunk c of env p(lo + j); "ca" / "cc" [C count, depth, 128]
+        the carries the rollout stored at the chunk starts; "rs" from `reset` [T, n] uint8, whose row
+        c L lands in row 0 of chunk c. seed None: env order."""
+        from . import ppo  # noqa: PLC0415
+
+        L, C = seq_len, T // seq_len
+        src = {k: rollout[name] for k, name in self.KEYS}
+        src["adv"], src["vt"] = ppo_inputs.advantages_t, ppo_inputs.value_targets_t
+        src["rs"] = reset
+        ca, cc = rollout["actor_carry_chunks"], rollout["critic_carry_chunks"]
+        dev = src["acts"].device
+        key = ("chunks", L, C, count, dev) + tuple((tuple(x.shape[2:]), x.dtype) for x in src.values())
+        key += (tuple(ca.shape[2:]), tuple(cc.shape[2:]))
+        b = self._buf.get(key)
+        if b is None:
+            b = {k: torch.empty((L, C * count) + tuple(x.shape[2:]), dtype=x.dtype, device=dev) for k, x in src.items()}
+            b["ca"] = torch.empty((C * count,) + tuple(ca.shape[2:]), dtype=ca.dtype, device=dev)
+            b["cc"] = torch.empty((C * count,) + tuple(cc.shape[2:]), dtype=cc.dtype, device=dev)
+            self._buf[key] = b
+        items = [(x, b[k], True) for k, x in src.items()]  # the time items, cut in chunks
+        items += [(ca, b["ca"].view((C, count) + tuple(ca.shape[2:]))), (cc, b["cc"].view((C, count) + tuple(cc.shape[2:])))]
+        ppo.gather_minibatch(items, n, lo, count, shuffle_seed=seed, epoch=epoch, seq_len=L)
+        return b
+
+
+def _chunk_count(rollout, T: int, n: int, seq_len, actor: GruPolicy, critic: GruPolicy):
+    """update(seq_len=)'s checks. None: the whole-sequence path (seq_len None or T). Else C = T / seq_len,
+    after checking that the rollout carries both networks' chunk carries [C, n, depth, 128]
+    (PolicyRollout.run(carry_every=seq_len) with the in-loop critic)."""
+    if seq_len is None:
+        return None
+    if int(seq_len) != seq_len or seq_len < 1 or T % int(seq_len):
+        raise ZbError(f"seq_len={seq_len!r} must be an integer >= 1 that divides the rollout's T = {T}")
+    if int(seq_len) == T:
+        return None
+    C = T // int(seq_len)
+    for name, h in (("actor_carry_chunks", actor), ("critic_carry_chunks", critic)):
+        x = rollout.get(name)
+        if x is None:
+            raise ZbError(f"seq_len={seq_len} needs rollout[{name!r}]: run the rollout with carry_every={seq_len}"
+                          + (" and the in-loop critic" if h.kind != ACTOR else ""))
+        if tuple(x.shape) != (C, n, h.shape.depth, 128) or not x.is_contiguous():
+            raise ZbError(f"rollout[{name!r}] must be a contiguous [C = T / seq_len = {C}, n = {n}, depth = "
+                          f"{h.shape.depth}, 128] tensor, got {list(x.shape)}")
+    return C
+
+
+def _reset_rows(torch, rollout, reset, T, n):
+    """update()'s `reset` as [T, n] uint8: the given rows, or row 0 zeros and row t done[t - 1]."""
+    if reset is None:
+        reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
+        reset[1:] = rollout["done"][:T - 1]
+    elif reset.dtype != torch.uint8:
+        reset = reset.to(torch.uint8)
+    return reset
+
 
 class PpoLearner:
     """num_passes x env-axis minibatches of AdamW steps behind a global-norm clip
@@ -203,7 +262,7 @@ class PpoLearner:
 
     def update(self, rollout: dict, ppo_inputs, actor: TrainablePolicy, critic: TrainablePolicy, actor_carry0,
                critic_carry0, reset=None, num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE,
-               **loss_kw) -> list:
+               seq_len: int | None = None, **loss_kw) -> list:
         """One PPO update of `actor` and `critic` on a finished rollout (the optimizer state is kept
         between updates of the same pair).
 
@@ -214,7 +273,13 @@ class PpoLearner:
         the previous run's last done flags or None -> zeros; row t: done[t - 1]).
         Minibatches are contiguous env slices of `batch_size` in env order, or with a shuffle_seed
         the same positions of the pass's keyed permutation (ksim shuffles them with its own RNG
-        [U]). Returns the losses, one per optimizer step."""
+        [U]). Returns the losses, one per optimizer step.
+
+        seq_len = L < T (a divisor of T): truncated BPTT with stored carries. The
+        same envs per minibatch, each as its T / L chunks of L steps; the networks run on
+        [L, (T / L) b] from rollout["actor_carry_chunks"] / ["critic_carry_chunks"]
+        (PolicyRollout.run(carry_every=L)), which are data: no gradient crosses a chunk start, and
+        actor_carry0 / critic_carry0 are not read. seq_len None or T: the whole sequences, as ever."""
         torch = self.torch
         if self.opt is None or actor is not self.actor or critic is not self.critic:
             self.actor, self.critic = actor, critic
@@ -223,8 +288,11 @@ class PpoLearner:
                                          weight_decay=self.weight_decay)
         T = rollout["actions"].shape[0]
         n = rollout["actions"].shape[1]
+        if _chunk_count(rollout, T, n, seq_len, actor.policy, critic.policy) is not None:
+            return self._update_gathered(rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes,
+                                         batch_size, loss_kw, seq_len=int(seq_len))
         if self.shuffle_seed is not None:
-            return self._update_shuffled(rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes,
+            return self._update_gathered(rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes,
                                          batch_size, loss_kw)
         if reset is None:
             reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
@@ -253,17 +321,27 @@ class PpoLearner:
         self.critic.sync()
         return losses
 
-    def _update_shuffled(self, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes, batch_size,
-                         loss_kw) -> list:
-        """update() over the keyed permutation's minibatches: the same steps on gathered buffers."""
+    def _update_gathered(self, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, num_passes, batch_size,
+                         loss_kw, seq_len=None) -> list:
+        """update() on minibatches cut by the gather, the same steps on its buffers: with a shuffle seed
+        the positions of the pass's keyed permutation, without one (seq_len alone) env order; with
+        seq_len the buffers hold the minibatch in chunks. The pass count advances either way, as in
+        update()'s env-slice path."""
         torch = self.torch
-        if reset is not None and reset.dtype != torch.uint8:
-            reset = reset.to(torch.uint8)
+        if seq_len is not None:
+            reset = _reset_rows(torch, rollout, reset, T, n)  # the chunked gather cuts given rows
+        elif reset is not None and reset.dtype != torch.uint8:
+            reset = reset.to(torch.uint8)  # reset None: the gather builds the rows itself
         losses = []
         for _ in range(num_passes):
             for lo in range(0, n, batch_size):
-                b = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo,
-                                 min(n, lo + batch_size) - lo, self.shuffle_seed, self.epoch)
+                count = min(n, lo + batch_size) - lo
+                if seq_len is not None:
+                    b = self._mb.cut_chunks(torch, rollout, ppo_inputs, reset, T, n, lo, count, self.shuffle_seed,
+                                            self.epoch, seq_len)
+                else:
+                    b = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo, count,
+                                     self.shuffle_seed, self.epoch)
                 lp = self.actor.log_prob(b["obs_a"], b["acts"], b["ca"], b["rs"])
                 v = self.critic.value(b["obs_c"], b["cc"], b["rs"])
                 loss = ppo_loss(lp, b["old_lp"], b["adv"], v, b["old_v"], b["vt"], **loss_kw)
@@ -335,18 +413,20 @@ class HipPpoLearner:
             return self.shuffle_seed
         return (int(self.shuffle_seed) + RANK_SEED_STRIDE * self.rank) % (1 << 64)
 
-    def check_ranks(self, n_local: int, T: int, batch_size: int, num_passes: int) -> None:
+    def check_ranks(self, n_local: int, T: int, batch_size: int, num_passes: int, seq_len: int | None = None) -> None:
         """With several ranks: raise ZbError unless batch_size is a multiple of the world size and all
-        ranks agree on (n_local, T, batch_size, num_passes, shuffle_seed, learning_rate) - one small
-        all_gather, no GPU work over gloo. update() runs it once per such shape."""
-        key = (int(n_local), int(T), int(batch_size), int(num_passes))
+        ranks agree on (n_local, T, batch_size, num_passes, seq_len, shuffle_seed, learning_rate) - one
+        small all_gather, no GPU work over gloo. update() runs it once per such shape. seq_len None
+        counts as T: the same path."""
+        key = (int(n_local), int(T), int(batch_size), int(num_passes), int(T if seq_len is None else seq_len))
         if self.world == 1 or self._agreed == key:
             return
         from .dist import agree  # noqa: PLC0415
 
         seed = -1 if self.shuffle_seed is None else int(self.shuffle_seed) % (1 << 64)
         lr = struct.unpack("<q", struct.pack("<d", float(self.learning_rate)))[0]
-        agree(dict(n_local=key[0], T=key[1], batch_size=key[2], num_passes=key[3], shuffle=int(seed >= 0),
+        agree(dict(n_local=key[0], T=key[1], batch_size=key[2], num_passes=key[3], seq_len=key[4],
+                   shuffle=int(seed >= 0),
                    shuffle_seed_low=seed & 0xFFFFFFFF, shuffle_seed_high=(seed >> 32) & 0xFFFFFFFF if seed >= 0 else 0,
                    learning_rate_bits=lr), f"HipPpoLearner over {self.world} ranks", self.group)
         if key[2] % self.world:
@@ -389,12 +469,15 @@ class HipPpoLearner:
                 self._buf["sums"] = torch.empty(self.world, 4, dtype=torch.float64, device=dev)
 
     def update(self, rollout: dict, ppo_inputs, actor, critic, actor_carry0, critic_carry0, reset=None,
-               num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, **loss_kw) -> list:
+               num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE,
+               seq_len: int | None = None, **loss_kw) -> list:
         """One PPO update, as PpoLearner.update (same arguments, same minibatches in the same order,
         shuffled by the same permutation when both have the same shuffle_seed).
         Returns one float64 device tensor [6] per optimizer step: zb_ppo_loss's four sums (sum S,
         sum Vt, sum clipped, sum kl), then the row count and value_loss_coef the step used; loss(sums)
-        forms the scalar loss from it. Nothing is synchronized."""
+        forms the scalar loss from it. Nothing is synchronized.
+        seq_len: as PpoLearner.update's (truncated BPTT on the rollout's stored chunk carries; the
+        loss still runs over the minibatch's T b rows, so the row count in the sums is unchanged)."""
         from . import ppo  # noqa: PLC0415
 
         torch = self.torch
@@ -405,18 +488,21 @@ class HipPpoLearner:
         T = rollout["actions"].shape[0]
         n = rollout["actions"].shape[1]
         W = self.world
+        # how a minibatch is cut: in chunks by the chunked gather, by the whole-sequence gather, or as env slices
+        if _chunk_count(rollout, T, n, seq_len, act, cri) is not None:
+            mode = "chunks"
+        else:
+            mode = "slices" if self.shuffle_seed is None else "gather"
         if W > 1:
             from .dist import all_gather_rows  # noqa: PLC0415
 
-            self.check_ranks(n, T, batch_size, num_passes)
+            self.check_ranks(n, T, batch_size, num_passes, seq_len)
             batch_size //= W  # this rank's share of every minibatch
-        shuffled = self.shuffle_seed is not None
         seed = self.rank_seed()
-        if reset is None and not shuffled:
-            reset = torch.zeros(T, n, dtype=torch.uint8, device=rollout["actions"].device)
-            reset[1:] = rollout["done"][:T - 1]
-        if shuffled and reset is not None and reset.dtype != torch.uint8:
-            reset = reset.to(torch.uint8)
+        if mode == "chunks" or (mode == "slices" and reset is None):
+            reset = _reset_rows(torch, rollout, reset, T, n)
+        elif mode == "gather" and reset is not None and reset.dtype != torch.uint8:
+            reset = reset.to(torch.uint8)  # reset None: the gather builds the rows itself
         coef = float(loss_kw.get("value_loss_coef", DEFAULT_VALUE_LOSS_COEF))
         out = []
         for _ in range(num_passes):
@@ -426,9 +512,13 @@ class HipPpoLearner:
                 def cut(x):
                     return x[:T, lo:hi].contiguous()
 
-                if shuffled:
-                    mb = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo, hi - lo,
-                                      seed, self.epoch)
+                if mode != "slices":
+                    if mode == "chunks":
+                        mb = self._mb.cut_chunks(torch, rollout, ppo_inputs, reset, T, n, lo, hi - lo, seed, self.epoch,
+                                                 int(seq_len))
+                    else:
+                        mb = self._mb.cut(torch, rollout, ppo_inputs, actor_carry0, critic_carry0, reset, T, n, lo,
+                                          hi - lo, seed, self.epoch)
                     obs_a, acts, obs_c, rs, ca, cc = mb["obs_a"], mb["acts"], mb["obs_c"], mb["rs"], mb["ca"], mb["cc"]
                     old_lp, adv, old_v, vt = mb["old_lp"], mb["adv"], mb["old_v"], mb["vt"]
                 else:
@@ -439,7 +529,7 @@ class HipPpoLearner:
                 sums = torch.empty(6, dtype=torch.float64, device=lp.device)
                 total = T * (hi - lo) * W  # the rows of this minibatch on all ranks
                 sums[4], sums[5] = float(total), coef
-                if not shuffled:
+                if mode == "slices":
                     old_lp, adv, old_v, vt = (cut(rollout["log_prob"]), cut(ppo_inputs.advantages_t),
                                               cut(rollout["value"]), cut(ppo_inputs.value_targets_t))
                 d_lp, d_v, _ = ppo.ppo_loss_grad(lp, old_lp, adv, v, old_v, vt, sums=sums,

@@ -425,7 +425,8 @@ class PolicyRollout:
         self.done = None
 
     def run(self, T: int, record_critic: bool = False, critic: GruPolicy | None = None,
-            critic_carry=None, record_terms: bool = False, mode: int = SAMPLE) -> dict:
+            critic_carry=None, record_terms: bool = False, mode: int = SAMPLE,
+            carry_every: int | None = None) -> dict:
         """T control steps. With record_critic, out["obs_critic"][t] is the critic observation of
         the state the actor acted in at step t (what get_ppo_variables evaluates the critic on,
         train.py:1683-1729) and out["obs_critic_next"] that of the state after step T-1 (the
@@ -445,10 +446,19 @@ class PolicyRollout:
         out["command_terms"] [T, n, 5] holds the tracking terms (cs.CMD_TERM_NAMES), read with
         zb_get_command_terms on the group's own stream right after each step. Every other output
         keeps its bits. `mode`: SAMPLE, or MODE for the deterministic rollout of the mixture's mode
-        (the actor's log-probs are then those of the mode actions)."""
+        (the actor's log-probs are then those of the mode actions).
+
+        With carry_every = L (a divisor of T; truncated BPTT), out["actor_carry_chunks"]
+        [T / L, n, depth, 128] row c is the actor carry as it stood before step c L's actor launch,
+        i.e. before that step's reset row is applied (row 0: the carry on entry), and with an in-loop
+        critic out["critic_carry_chunks"] the same of the critic carry: one copy each per chunk on the
+        group's own stream, in front of the launch. Every other output keeps its bits; without it
+        nothing is allocated or issued."""
         torch = self.actor.torch
         if mode not in (SAMPLE, MODE):
             raise ZbError("PolicyRollout.run: mode is SAMPLE or MODE")
+        if carry_every is not None and (int(carry_every) != carry_every or carry_every < 1 or T % carry_every):
+            raise ZbError(f"PolicyRollout.run: carry_every={carry_every!r} must be an integer >= 1 that divides T = {T}")
         n, dev = self.eng.n, self.eng.device
         if self.obs is None:
             self.reset()
@@ -476,6 +486,12 @@ class PolicyRollout:
             terms = torch.empty(T, n, cs.NUM_TERMS, **f32)
             if getattr(self.eng, "command_cfg", None) is not None:
                 cterms = torch.empty(T, n, cs.NUM_CMD_TERMS, **f32)
+        a_chunks = c_chunks = None
+        if carry_every is not None:
+            carry_every = int(carry_every)
+            a_chunks = torch.empty((T // carry_every,) + tuple(self.carry.shape), **f32)
+            if critic is not None:
+                c_chunks = torch.empty((T // carry_every,) + tuple(critic_carry.shape), **f32)
         L = self.eng.L
         # an EnvGroups engine runs each group's actor -> zb_step chain on the group's own stream
         # (DESIGN.md §4f); a HipEngine is one group on the current stream
@@ -493,6 +509,8 @@ class PolicyRollout:
                     r = done[t - 1][lo:hi] if t > 0 else (None if self.done is None else self.done[lo:hi])
                     if self.stagger and grouped and t == 0 and g > 0:
                         s.wait_event(prev_actor)
+                    if a_chunks is not None and t % carry_every == 0:
+                        a_chunks[t // carry_every][lo:hi].copy_(self.carry[lo:hi])
                     self.actor.actor(obs[t][lo:hi], self.carry[lo:hi], reset=r, mode=mode, seed=self.seed,
                                      env_offset=e.env_offset, step=self.step_count, actions=acts[t][lo:hi],
                                      log_prob=lp[t][lo:hi])
@@ -511,6 +529,8 @@ class PolicyRollout:
                                                        terms[0][lo:hi].data_ptr() if record_terms else None,
                                                        float(self.curriculum), stream))
                     if critic is not None:  # V(s_t): its input crit[t] is ready since step t-1
+                        if c_chunks is not None and t % carry_every == 0:
+                            c_chunks[t // carry_every][lo:hi].copy_(critic_carry[lo:hi])
                         critic.critic(crit[t][lo:hi], critic_carry[lo:hi],
                                       reset=done[t - 1][lo:hi] if t > 0 else None, value=val[t][lo:hi])
                         if t == T - 1:  # the bootstrap V(s_T)
@@ -535,4 +555,8 @@ class PolicyRollout:
             out["reward_terms"] = terms
             if cterms is not None:
                 out["command_terms"] = cterms
+        if a_chunks is not None:
+            out["actor_carry_chunks"] = a_chunks
+        if c_chunks is not None:
+            out["critic_carry_chunks"] = c_chunks
         return out

@@ -459,39 +459,63 @@ def minibatch_perm_host(n: int, seed: int, epoch: int = 0):
     return out
 
 
-def _gather_table(items, n, count, describe):
+def _gather_table(items, n, count, describe, seq_len=None):
     """The ZbGatherItem array of `items`, pairs (src, dst): dst [rows, count, ...] dense, src
     [>= rows, n, ...] with the same trailing shape and dtype, dense below its first axis (any stride
-    along it), or None for zeros. `describe(x)` -> (address, shape, strides in bytes, itemsize, dtype)."""
+    along it), or None for zeros. `describe(x)` -> (address, shape, strides in bytes, itemsize, dtype).
+    With seq_len = L also the int32 `cut` array of zb_minibatch_gather_seq: an item given as a triple
+    (src, dst, True) is a time item, dst [L, C count, ...], of rows = L C cut in chunks; a pair is not."""
     items = list(items)
     if not 1 <= len(items) <= GATHER_MAX_ITEMS:
         raise ZbError(f"gather_minibatch takes 1 to {GATHER_MAX_ITEMS} items, got {len(items)}")
     table = (ZbGatherItem * len(items))()
-    for k, (src, dst) in enumerate(items):
+    cut = None if seq_len is None else (C.c_int32 * len(items))()  # the plain gather does what it always did
+    for k, item in enumerate(items):
+        if len(item) not in (2, 3):
+            raise ZbError(f"item {k}: (src, dst), or (src, dst, True) for a time item cut in chunks of seq_len")
+        src, dst = item[0], item[1]
         dp, dshape, dstr, isz, ddt = describe(dst)
-        if len(dshape) < 2 or dshape[1] != count or dshape[0] < 1:
+        chunks = 1
+        if len(item) == 3 and item[2]:
+            if cut is None:
+                raise ZbError(f"item {k} is marked as a time item to be cut in chunks, but no seq_len is given")
+            if len(dshape) < 2 or dshape[0] != seq_len or dshape[1] < count or dshape[1] % count:
+                raise ZbError(f"item {k}: a time item's dst must be [seq_len = {seq_len}, C x {count}, ...], got "
+                              f"{list(dshape)}")
+            chunks = dshape[1] // count
+            cut[k] = 1
+        elif len(dshape) < 2 or dshape[1] != count or dshape[0] < 1:
             raise ZbError(f"item {k}: dst must be [rows, {count}, ...], got {list(dshape)}")
         dense = [isz] * len(dshape)
         for a in range(len(dshape) - 2, -1, -1):
             dense[a] = dense[a + 1] * dshape[a + 1]
         if any(st != dn for st, dn, sz in zip(dstr, dense, dshape) if sz != 1):  # a size-1 axis has no stride
             raise ZbError(f"item {k}: dst must be contiguous")
-        rows, row_bytes = dshape[0], dense[1]
+        rows, row_bytes = dshape[0] * chunks, dense[1]
         sp, stride = None, 0
         if src is not None:
             sp, sshape, sstr, _, sdt = describe(src)
             if (sdt != ddt or len(sshape) != len(dshape) or sshape[0] < rows or sshape[1] != n
                     or tuple(sshape[2:]) != tuple(dshape[2:])):
                 raise ZbError(f"item {k}: src {list(sshape)} {sdt} does not feed dst {list(dshape)} {ddt} over "
-                              f"{n} envs")
+                              f"{n} envs" + (f" in {chunks} chunks of seq_len={seq_len}" if cut is not None and cut[k] else ""))
             if any(st != dn for st, dn, sz in zip(sstr[1:], dense[1:], sshape[1:]) if sz != 1) or sstr[0] < 0:
                 raise ZbError(f"item {k}: src must be dense below its first axis")
             stride = sstr[0] if rows > 1 else 0
         table[k] = ZbGatherItem(sp, dp, rows, row_bytes, stride)
-    return table
+    return table, cut
 
 
-def gather_minibatch(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0) -> None:
+def _seq_len(seq_len):
+    if seq_len is None:
+        return None
+    if int(seq_len) != seq_len or int(seq_len) < 1:
+        raise ZbError(f"gather_minibatch: seq_len must be an integer >= 1, got {seq_len!r}")
+    return int(seq_len)
+
+
+def gather_minibatch(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0,
+                     seq_len: int | None = None) -> None:
     """zb_minibatch_gather: one launch that cuts every array of a minibatch. For each pair (src, dst)
     of `items` (device tensors; at most 16) and every t < rows, j < count:
     dst[t, j] = src[t, p(lo + j)], p = minibatch_perm(n, shuffle_seed, epoch), or the identity (a
@@ -499,7 +523,13 @@ def gather_minibatch(items, n: int, lo: int, count: int, shuffle_seed: int | Non
     of the same dtype and trailing shape, dense below its first axis (the first T rows of a [T + 1]
     buffer, or any stride along time), or None, which fills dst with zeros. A per-env array such as
     a carry goes in as src[None], dst[None]. Asynchronous on the current stream; allocates nothing
-    on the device."""
+    on the device.
+
+    seq_len = L (zb_minibatch_gather_seq, truncated BPTT): an item given as (src, dst, True) is a time
+    item, dst [L, C count, ...], whose T = L C source rows are cut in C chunks,
+    dst[l, c count + j] = src[c L + l, p(lo + j)]; a pair (src, dst) moves as above (the carries stored
+    at the chunk starts: src [C, n, ...], dst [C, count, ...], then viewed as the C count sequences'
+    carry0)."""
     import torch  # noqa: PLC0415
 
     items = list(items)
@@ -514,14 +544,22 @@ def gather_minibatch(items, n: int, lo: int, count: int, shuffle_seed: int | Non
         return x.data_ptr(), tuple(x.shape), tuple(s * isz for s in x.stride()), isz, x.dtype
 
     n, seed, epoch = _perm_args(n, 0 if shuffle_seed is None else shuffle_seed, epoch)
-    table = _gather_table(items, n, int(count), describe)
+    seq_len = _seq_len(seq_len)
+    table, cut = _gather_table(items, n, int(count), describe, seq_len)
+    shuffle = 0 if shuffle_seed is None else 1
     with torch.cuda.device(dev):
-        _check(load_library().zb_minibatch_gather(table, len(table), n, int(lo), int(count),
-                                                  0 if shuffle_seed is None else 1, seed, epoch, _stream(torch, dev)))
+        if seq_len is None:
+            _check(load_library().zb_minibatch_gather(table, len(table), n, int(lo), int(count), shuffle, seed, epoch,
+                                                      _stream(torch, dev)))
+        else:
+            _check(load_library().zb_minibatch_gather_seq(table, cut, len(table), seq_len, n, int(lo), int(count),
+                                                          shuffle, seed, epoch, _stream(torch, dev)))
 
 
-def gather_minibatch_host(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0) -> None:
-    """zb_minibatch_gather_host: gather_minibatch on numpy arrays (or CPU tensors), in place on each dst."""
+def gather_minibatch_host(items, n: int, lo: int, count: int, shuffle_seed: int | None = None, epoch: int = 0,
+                          seq_len: int | None = None) -> None:
+    """zb_minibatch_gather_host (with seq_len: zb_minibatch_gather_seq_host): gather_minibatch on numpy
+    arrays (or CPU tensors), in place on each dst."""
     import numpy as np  # noqa: PLC0415
 
     def describe(x):
@@ -534,9 +572,14 @@ def gather_minibatch_host(items, n: int, lo: int, count: int, shuffle_seed: int 
         return x.ctypes.data, x.shape, x.strides, x.itemsize, x.dtype
 
     n, seed, epoch = _perm_args(n, 0 if shuffle_seed is None else shuffle_seed, epoch)
-    table = _gather_table(list(items), n, int(count), describe)
-    _check(load_library().zb_minibatch_gather_host(table, len(table), n, int(lo), int(count),
-                                                   0 if shuffle_seed is None else 1, seed, epoch))
+    seq_len = _seq_len(seq_len)
+    table, cut = _gather_table(list(items), n, int(count), describe, seq_len)
+    shuffle = 0 if shuffle_seed is None else 1
+    if seq_len is None:
+        _check(load_library().zb_minibatch_gather_host(table, len(table), n, int(lo), int(count), shuffle, seed, epoch))
+    else:
+        _check(load_library().zb_minibatch_gather_seq_host(table, cut, len(table), seq_len, n, int(lo), int(count),
+                                                           shuffle, seed, epoch))
 
 
 def _host(a, dtype, name, writable=False):

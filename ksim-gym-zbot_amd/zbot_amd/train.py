@@ -4,7 +4,7 @@ update in HIP, the episode-length curriculum.
 
     tr = Trainer(engine, actor, critic, rollout_steps=200, num_passes=4, batch_size=128,
                  seed=0, shuffle=True, curriculum=EpisodeLengthCurriculum(), ctrl_dt=0.02, group=None,
-                 command_config=None, telemetry=False, **learner_kw)
+                 command_config=None, telemetry=False, seq_len=None, **learner_kw)
     m = tr.step()            # one iteration; returns metrics (telemetry=True: with m["telemetry"])
     v = tr.validate()        # a rollout without an update: its telemetry; the Trainer stays where it was
     sd = tr.state_dict(); tr.load_state_dict(sd)
@@ -30,6 +30,10 @@ One step(), in order:
   6. curriculum.rollout_episode_length and curriculum.update: the iteration's one host
      synchronisation is that float;
   7. the new level goes to the next rollout.
+With seq_len = L < rollout_steps (a divisor of it) the update is truncated BPTT: 3.
+runs with carry_every=L, which stores both carries at every chunk start, and 5. with seq_len=L, which
+trains on each env's T / L chunks as separate sequences from those stored carries; seq_len None or
+rollout_steps is the whole-sequence path, the same launches and bits as without the argument.
 With telemetry=True the rollout of 3. also records the reward and command terms, and between 4. and
 5. one ppo.rollout_summary on the current stream reduces them, the rewards, the episode ends, the
 log-probs, the values and the value targets to 32 sums; telemetry=False issues none
@@ -63,8 +67,12 @@ class Trainer:
                  num_passes: int = DEFAULT_NUM_PASSES, batch_size: int = DEFAULT_BATCH_SIZE, seed: int = 0,
                  shuffle: bool = True, curriculum: EpisodeLengthCurriculum | None = None, ctrl_dt: float = 0.02,
                  group=None, command_config: cs.ZbCommandConfig | None = None, telemetry: bool = False,
-                 **learner_kw):
-        """telemetry: step() also returns "telemetry", metrics.rollout_telemetry of the rollout's
+                 seq_len: int | None = None, **learner_kw):
+        """seq_len: train on chunks of seq_len steps from the carries the rollout stored at the chunk
+        starts (truncated BPTT; must divide rollout_steps; None: whole sequences). validate() stores
+        none. It is part of state_dict() when set, and the ranks must agree on it; seq_len == rollout_steps
+        is None in every one of these respects.
+        telemetry: step() also returns "telemetry", metrics.rollout_telemetry of the rollout's
         sums (every reward and command term, how episodes end, the entropy estimate, the explained
         variance, the episode statistics). On several ranks the 32 sums go through
         dist.reduce_fixed_order: every rank then reports the same bits, but they are a rank-order
@@ -80,6 +88,11 @@ class Trainer:
         self.torch = actor.torch
         self.eng, self.actor, self.critic = engine, actor, critic
         self.T, self.num_passes, self.batch_size = int(rollout_steps), int(num_passes), int(batch_size)
+        if seq_len is not None and (int(seq_len) != seq_len or seq_len < 1 or self.T % int(seq_len)):
+            raise ZbError(f"seq_len={seq_len!r} must be an integer >= 1 that divides rollout_steps = {self.T}")
+        # seq_len == rollout_steps is the whole-sequence path: kept as None, so that the ranks' agreement,
+        # state_dict() and load_state_dict() see one spelling of it
+        self.seq_len = None if seq_len is None or int(seq_len) == self.T else int(seq_len)
         self.seed, self.shuffle, self.ctrl_dt = int(seed), bool(shuffle), float(ctrl_dt)
         self.group, self.world, self.rank = group, 1, 0
         if group is not None:
@@ -92,7 +105,8 @@ class Trainer:
                 raise ZbError(f"rank {self.rank} of {self.world} owns envs from {self.rank * int(engine.n)}: the engine "
                               f"was created with env_offset {engine.env_offset}")
             agree(dict(seed=self.seed % (1 << 63), shuffle=int(self.shuffle), rollout_steps=self.T,
-                       num_passes=self.num_passes, batch_size=self.batch_size, envs_per_rank=int(engine.n)),
+                       num_passes=self.num_passes, batch_size=self.batch_size, envs_per_rank=int(engine.n),
+                       seq_len=0 if self.seq_len is None else self.seq_len),
                   f"Trainer over {self.world} ranks", group)
         self.telemetry = bool(telemetry)
         self.command_config = command_config
@@ -133,10 +147,11 @@ class Trainer:
         level = self.cur_state.level
         ro.curriculum = level
         self._mark("rollout", False)
-        if self.telemetry:
-            out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry, record_terms=True)
-        else:
-            out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry)
+        # only what is asked for is passed on: without telemetry and seq_len this is the call it always was
+        extra_kw = dict(record_terms=True) if self.telemetry else {}
+        if self.seq_len is not None:
+            extra_kw["carry_every"] = self.seq_len
+        out = ro.run(T, record_critic=True, critic=self.critic, critic_carry=self.critic_carry, **extra_kw)
         self._mark("rollout", True)
         self._mark("ppo_inputs", False)
         inputs = ppo.compute_ppo_inputs(out["value"], out["reward"], out["done"], out["success"],
@@ -148,7 +163,7 @@ class Trainer:
             reset = torch.cat([prev_done[None], out["done"][:T - 1]])
         self._mark("update", False)
         sums = self.learner.update(out, inputs, self.actor, self.critic, carry0, ccarry0, reset=reset,
-                                   num_passes=self.num_passes, batch_size=self.batch_size)
+                                   num_passes=self.num_passes, batch_size=self.batch_size, seq_len=self.seq_len)
         self._mark("update", True)
         stats = self.eng.get_stats()
         length = rollout_episode_length(stats, self.eng.get_state(), out["done"][T - 1], self.ctrl_dt,
@@ -260,7 +275,8 @@ class Trainer:
             learner=None if self.learner.state is None else self.learner.state_dict(),
             curriculum=dict(level=float(self.cur_state.level), steps=int(self.cur_state.steps)),
             iteration=int(self.iteration), seed=self.seed, shuffle=self.shuffle, world=self.world, rank=self.rank,
-            command_config=None if self.command_config is None else bytes(self.command_config))
+            command_config=None if self.command_config is None else bytes(self.command_config),
+            **({} if self.seq_len is None else dict(seq_len=self.seq_len)))
 
     def load_state_dict(self, sd: dict) -> None:
         """Restore state_dict()'s result into this Trainer's engine, handles and learner."""
@@ -272,6 +288,8 @@ class Trainer:
                           f"seed {self.eng.seed}")
         if int(sd["seed"]) != self.seed or bool(sd["shuffle"]) != self.shuffle:
             raise ZbError(f"the state was trained with seed={sd['seed']}, shuffle={sd['shuffle']}")
+        if sd.get("seq_len") != self.seq_len:
+            raise ZbError(f"the state was trained with seq_len={sd.get('seq_len')}; this Trainer has seq_len={self.seq_len}")
         if int(sd.get("world", 1)) != self.world or int(sd.get("rank", 0)) != self.rank:
             raise ZbError(f"the state is rank {sd.get('rank', 0)}'s of {sd.get('world', 1)}; this Trainer is rank "
                           f"{self.rank} of {self.world}")
